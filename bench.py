@@ -1,6 +1,14 @@
 """bench.py — ray-samples/s (fwd+bwd) of one NICE-SLAM mapping iteration, Replica room0 shape.
 
-python bench.py [--gpus N --steps K --warmup W]   (N>1: launched by torch.distributed.run)
+python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+(N>1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step).
+--dump-outputs DIR then runs the timed path for one more step from the seeded start and writes what
+that step computed as DIR/<name>.npy, the same arrays every run (dump_outputs).
+--full adds everything else to the line: per-kernel HIP-event spans and rooflines (extra eager
+iterations), the reference entry points, stress, bulk and frame-IO legs (child processes) and the CPU /
+reference-path baselines; --no-cpu-baseline, --no-stress, --no-frames and --no-bulk trim a --full run.
 
 One step (the headline `value`) = one colour-stage iteration of the mapping engine that
 Mapper.optimize_map's inner loop runs on (engine.MappingEngine.iteration: src/Mapper.py:391-519's
@@ -211,7 +219,9 @@ class StepGraphs:
     graph, so the launch bubble between two graph replays (~20 us on MI355X: the next replay starts
     only after the previous one has drained) is paid once per block; two single-iteration graphs
     (one per ray-buffer parity of the prefetching engine) cover remainders.  run(k) executes exactly
-    k iterations; finish() re-aligns the engine's host-side buffer parity (sync) with the device."""
+    k iterations; finish() re-aligns the engine's host-side buffer parity (sync) with the device.
+    `last` is what fn returned for the most recently replayed iteration (the graph's own output
+    tensors, overwritten by that graph's next replay)."""
 
     def __init__(self, fn, block=GRAPH_BLOCK, sync=None):
         side = torch.cuda.Stream()
@@ -220,28 +230,33 @@ class StepGraphs:
             for _ in range(2):
                 fn()
         torch.cuda.current_stream().wait_stream(side)
-        self.single = []
+        self.single, self.single_out = [], []
         # thread_local capture: RCCL's watchdog thread polls its work events while this thread captures
         # (global mode makes that poll fail the capture: hipErrorStreamCaptureUnsupported)
         for _ in range(2):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                fn()
+                out = fn()
             self.single.append(g)
+            self.single_out.append(out)
         self.block = max(2, block - block % 2)
         self.blockg = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.blockg, capture_error_mode="thread_local"):
             for _ in range(self.block):
-                fn()
+                out = fn()
+        self.block_out = out
+        self.last = None
         self.par = 0  # device-side parity relative to the capture start
         self.sync = sync
 
     def run(self, k=1):
         while self.par == 0 and k >= self.block:
             self.blockg.replay()
+            self.last = self.block_out
             k -= self.block
         for _ in range(k):
             self.single[self.par].replay()
+            self.last = self.single_out[self.par]
             self.par ^= 1
 
     def __call__(self):
@@ -377,7 +392,8 @@ class Room0Scene:
         """One colour-stage mapping iteration, no host synchronisation (hipGraph-capturable).
         Pixels are drawn inside the gather kernel (uniform over the image, like select_uv) and
         the gather kernel adds the kept-ray count into self.kept: kept ray-samples over a run =
-        self.kept × samples per ray, read once after the timed region."""
+        self.kept × samples per ray, read once after the timed region.  Returns what the iteration
+        hands its caller, by name (device tensors; the engine's are valid until the next step)."""
         if self.path != "fused":
             return self.step_autograd(stage, sharded)
         cfg = self.cfg
@@ -387,10 +403,11 @@ class Room0Scene:
         # gathering its slice; the gather kernel also yields the global batch's max(gt_depth), so
         # the only collective of the iteration is the gradient exchange
         world = int(os.environ.get("WORLD_SIZE", "1")) if sharded else 1
-        self.engine.iteration(
+        ray_loss, keep = self.engine.iteration(
             stage, self.frames, None, n, (H, W), (cfg["fx"], cfg["fy"], cfg["cx"], cfg["cy"]), self.opt,
             trainable_decoders=("color",), exchange=self.exchange if sharded else None, n_kept=self.kept,
             seed=1000, world=world, rank=self.rank if sharded else 0, prefetch=PREFETCH)
+        return {"ray_loss": ray_loss, "keep": keep}
 
     def flip_parity(self):
         """The prefetching engine's host-side ray-buffer parity, after an odd number of replayed
@@ -404,7 +421,7 @@ class Room0Scene:
         The inside-mask prefilter (Mapper.py:469-481) removes rays; here they stay in the batch
         with zero loss weight (their gradients are exactly zero) and the sampler's batch-global
         max(gt_depth) is taken over the kept rays only — the same maths without a host-side
-        compaction.  Returns the number of kept ray-samples (device tensor).
+        compaction.  Returns the rendered depth, uncertainty and colour and the keep mask, by name.
         """
         cfg = self.cfg
         D = pkg().distributed
@@ -428,6 +445,7 @@ class Room0Scene:
             D.allreduce_grads(D.optimizer_params(self.opt))
         self.opt.step()
         self.kept += keep.sum()
+        return {"depth": depth.detach(), "uncertainty": unc.detach(), "color": color.detach(), "keep": keep}
 
 
 class _Slam:
@@ -1091,6 +1109,70 @@ def slam_loop(dev, cfg=ROOM0, frames=60, warm_frames=10):
     return res
 
 
+DUMP_ROWS = 65536  # frustum rows of each grid kept by --dump-outputs (x 32 channels x 4 B = 8 MiB per grid)
+
+
+def trained_tensors(scene):
+    """Every tensor a step updates in place, apart from the optimiser's state: the grids and the
+    decoders' parameters (fused engine: the flat buffers and their MFMA-packed copies)."""
+    ts = list(scene.grids.values())
+    if scene.path == "fused":
+        for d in scene.engine.decs.values():
+            ts += [d.flat, d.packed]
+    else:
+        ts += list(scene.nice.parameters())
+    return ts
+
+
+@torch.no_grad()
+def restore_start(scene, snap):
+    """Put the map and decoders back to `snap` (clones of trained_tensors at construction) and the
+    optimiser's moments and step counts to zero, all in place (captured graphs hold the addresses).
+    The pixel-draw counter and a prefetched ray batch stay: they depend on the step count alone."""
+    torch.cuda.synchronize()
+    for t, s in zip(trained_tensors(scene), snap):
+        t.copy_(s)
+    for st in scene.opt.state.values():
+        for v in st.values():
+            if torch.is_tensor(v):
+                v.zero_()
+    torch.cuda.synchronize()
+
+
+def dump_outputs(scene, last, path):
+    """--dump-outputs: what one step of the timed path computes, as path/<name>.npy.  The step is the
+    last one the path runs: after the timed steps main() restores the seeded start (restore_start) and
+    runs the path once more, on the next ray batch of the draw sequence.  The timed steps themselves
+    cannot repeat from run to run: their grid gradients are summed by float atomics, and tens of Adam
+    iterations amplify the summation order (measured on MI355X, 72 iterations: 2e-4 relative L2 in the
+    ray loss, up to 4e-2 in the colour grid's rows); one step from a fixed start depends on the
+    arguments alone, up to that one step's rounding (three runs on MI355X: ray loss, keep mask and
+    decoder bit-identical, grid rows within 1e-7 relative L2, 6e-7 absolute).
+    Written: the step's return values (scene.step: the engine's per-ray loss and keep mask; the autograd
+    path's rendered depth / uncertainty / colour), the map it updated in place (per grid, the values of
+    a fixed seeded sample of at most DUMP_ROWS of the frustum rows Adam optimises, [rows, 32]; the dense
+    grids would be ~50 MB) and the colour decoder's parameters, flattened.  float64 tensors stay
+    float64, everything else is written as float32."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    out = dict(last or {})
+    for k in ("grid_middle", "grid_fine", "grid_color"):
+        rows = scene.rows[k].long()
+        if rows.numel() > DUMP_ROWS:
+            pick = torch.randperm(rows.numel(), generator=torch.Generator().manual_seed(5))[:DUMP_ROWS]
+            rows = rows[pick.sort().values.to(rows.device)]
+        g = scene.grids[k].detach()
+        out[k + "_rows"] = g.permute(0, 2, 3, 4, 1).reshape(-1, g.shape[1])[rows]
+    if scene.path == "fused":
+        out["color_decoder"] = scene.engine.decs["color"].param.detach().reshape(-1)
+    else:
+        out["color_decoder"] = torch.cat([p.detach().reshape(-1) for p in scene.nice.color_decoder.parameters()])
+    for name, t in out.items():
+        a = t.detach().to("cpu", dtype=torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def leg_main(leg):
     """One auxiliary measurement in this (child) process on cuda:0; prints one JSON object."""
     dev = torch.device("cuda", 0)
@@ -1154,6 +1236,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed path once more from the seeded start and write "
+                         "what that last step computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel spans and rooflines, the "
+                         "reference entry points, stress, bulk and frame-IO legs, CPU and reference-path "
+                         "baselines (each can be left out again with its --no-... option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--eager", action="store_true", help="no hipGraph capture")
     ap.add_argument("--serial-branches", action="store_true",
@@ -1212,6 +1301,7 @@ def main():
     if args.serial_branches and getattr(scene, "engine", None) is not None:
         scene.engine.concurrent = False
     sharded = world > 1 or args.force_exchange
+    start = [t.detach().clone() for t in trained_tensors(scene)] if args.dump_outputs else None
     for _ in range(args.warmup):
         scene.step(sharded=sharded)
     torch.cuda.synchronize()
@@ -1239,22 +1329,34 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    last = None
     t0 = time.perf_counter()
     if graph is not None:
         graph.run(args.steps)
+        last = graph.last
     else:
         for _ in range(args.steps):
-            scene.step(sharded=sharded)
+            last = scene.step(sharded=sharded)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
     samples = int(scene.kept) * (cfg["n_strat"] + cfg["n_surf"])
-    # per-kernel durations: HIP events around each C-ABI launch, on the launching stream, over
-    # extra eager steps of the same kernels (events cannot bracket single kernels inside a replay)
+    if args.dump_outputs:
+        # one more step of the same path from the seeded start: its outputs repeat from run to run
+        restore_start(scene, start)
+        if graph is not None:
+            graph.run(1)
+            last = graph.last
+        else:
+            last = scene.step(sharded=sharded)
+        if rank == 0:
+            dump_outputs(scene, last, args.dump_outputs)
     if graph is not None:
         graph.finish()
-    timers = span_timers(scene, max(5, args.steps // 4), sharded=sharded)
+    # per-kernel durations (--full): HIP events around each C-ABI launch, on the launching stream, over
+    # extra eager steps of the same kernels (events cannot bracket single kernels inside a replay)
+    timers = span_timers(scene, max(5, args.steps // 4), sharded=sharded) if args.full else None
     tot = torch.tensor([samples, dt], dtype=torch.float64, device=dev)
     if world > 1:
         s = tot[:1].clone()
@@ -1266,13 +1368,6 @@ def main():
         samples_all, dt_max = float(samples), dt
     if rank == 0:
         pts_per_step = samples / args.steps
-        qf = timers.get("query_fwd", {"avg_ms": float("nan")})
-        qb = timers.get("query_bwd", {"avg_ms": float("nan")})
-        # the dominant single launch (query_bwd is the span over its concurrent branches)
-        dom_name, dom = max(((k, v) for k, v in timers.items() if k in KERNEL_WORK),
-                            key=lambda kv: kv[1]["total_ms"])
-        roof = kernel_roofline(dom_name, dom["avg_ms"], pts_per_step)
-        per_kernel = {k: kernel_roofline(k, v["avg_ms"], pts_per_step) for k, v in timers.items() if k in KERNEL_WORK}
         out = {
             "metric": "ray-samples/sec (fwd+bwd) per mapping iter; frames/sec on Replica room0",
             "value": samples_all / dt_max, "unit": "ray-samples/s", "n_gpus": world, "steps": args.steps,
@@ -1284,14 +1379,22 @@ def main():
                                    "(5-frame window x 200), grids middle/fine/colour, Adam",
                        "global_batch": int(round(pts_per_step)) * world, "seq_len": 48,
                        "parallelism": f"rays sharded dp{world}, RCCL all-reduce of the frustum-row gradients"},
-            "roofline": roof,
-            "kernel_rooflines": per_kernel,
-            "kernels_ms": {k: round(v["avg_ms"], 4) for k, v in timers.items()},
-            "query_fwd_hbm_frac": (pts_per_step * BYTES_FWD_PER_SAMPLE / (qf["avg_ms"] * 1e-3) / 1e9) / HBM_PEAK_GBS
-            if "query_fwd" in timers else None,
             "graph_block": GRAPH_BLOCK,
-            "query_bwd_ms": qb["avg_ms"],
         }
+        if timers is not None:
+            qf = timers.get("query_fwd", {"avg_ms": float("nan")})
+            qb = timers.get("query_bwd", {"avg_ms": float("nan")})
+            # the dominant single launch (query_bwd is the span over its concurrent branches)
+            dom_name, dom = max(((k, v) for k, v in timers.items() if k in KERNEL_WORK),
+                                key=lambda kv: kv[1]["total_ms"])
+            out["roofline"] = kernel_roofline(dom_name, dom["avg_ms"], pts_per_step)
+            out["kernel_rooflines"] = {k: kernel_roofline(k, v["avg_ms"], pts_per_step)
+                                       for k, v in timers.items() if k in KERNEL_WORK}
+            out["kernels_ms"] = {k: round(v["avg_ms"], 4) for k, v in timers.items()}
+            out["query_fwd_hbm_frac"] = (
+                (pts_per_step * BYTES_FWD_PER_SAMPLE / (qf["avg_ms"] * 1e-3) / 1e9) / HBM_PEAK_GBS
+                if "query_fwd" in timers else None)
+            out["query_bwd_ms"] = qb["avg_ms"]
         if sharded and args.path == "fused":
             keys, dn = scene.engine.grads_for("color", ("color",))
             out["exchange_bytes_per_step"] = scene.exchange.payload_bytes(keys, dn)
@@ -1299,25 +1402,26 @@ def main():
             out["exchange_backend"] = dist.get_backend() if dist.is_initialized() else None
             out["exchange_forced_world1"] = bool(args.force_exchange)
             # the collectives' own HIP-event spans (eager iterations, branches serialised), per iteration
-            coll = {k: v for k, v in timers.items() if k.startswith("collective.")}
-            out["collective_ms_per_step"] = {k: round(v["total_ms"] / max(5, args.steps // 4), 4)
-                                             for k, v in coll.items()}
+            if timers is not None:
+                coll = {k: v for k, v in timers.items() if k.startswith("collective.")}
+                out["collective_ms_per_step"] = {k: round(v["total_ms"] / max(5, args.steps // 4), 4)
+                                                 for k, v in coll.items()}
             out["dense_grad_bytes_per_step"] = sum(v.numel() for v in scene.grids.values()) * 4
         # the auxiliary measurements run as child processes: a failure there (one run on a fresh
         # box ended in a host heap abort inside a later leg) cannot take the headline line with it
-        if world == 1 and not args.no_frames and args.path == "fused":
+        if args.full and world == 1 and not args.no_frames and args.path == "fused":
             out["room0"] = run_leg("frames")
             out["room0_slam_loop"] = run_leg("slam_loop")
             out["optimize_map"] = run_leg("optimize_map")
             out["scene0000_ba"] = run_leg("scene0000")
             out["apartment"] = run_leg("apartment")
-        if world == 1 and not args.no_stress:
+        if args.full and world == 1 and not args.no_stress:
             out["grid_query_stress"] = run_leg("stress")
             out["stress_iteration"] = run_leg("stress_iter")
-        if world == 1 and not args.no_bulk:
+        if args.full and world == 1 and not args.no_bulk:
             out["bulk_forward"] = run_leg("bulk")
             out["frame_io"] = run_leg("frame_io")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene)
             ref = reference_gpu_baseline(scene)
             out["reference_gpu_path"] = ref

@@ -25,18 +25,24 @@ def pkg():
     return load_pkg()
 
 
+def load_golden(stem):
+    """The arrays of tests/golden/<stem>.<i>.npz (a fixture set stored in parts, scenes.save_parts)."""
+    if GOLDEN not in sys.path:
+        sys.path.insert(0, GOLDEN)
+    import scenes
+    return scenes.load_parts(os.path.join(GOLDEN, stem))
+
+
 @pytest.fixture(scope="session")
 def tiny():
-    with np.load(os.path.join(GOLDEN, "tiny_scene.npz")) as z:
-        return {k: z[k] for k in z.files}
+    return load_golden("tiny_scene")
 
 
 @pytest.fixture(scope="session")
 def loop():
-    """tests/golden/loop_fixtures.npz: loop-level vectors from the reference's own Tracker / Mapper
+    """tests/golden/loop_fixtures.*.npz: loop-level vectors from the reference's own Tracker / Mapper
     code (tests/golden/make_golden_loop.py)."""
-    with np.load(os.path.join(GOLDEN, "loop_fixtures.npz")) as z:
-        return {k: z[k] for k in z.files}
+    return load_golden("loop_fixtures")
 
 
 class FixedPixels:

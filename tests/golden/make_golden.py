@@ -191,9 +191,9 @@ def main():
     for stage in orc.STAGES:
         out.update(np_dict(f"eval.{stage}.", eval_points_case(sd, grids, bound, stage, gen)))
     out.update(np_dict("composite.", composite_case(gen)))
-    path = os.path.join(HERE, "tiny_scene.npz")
-    np.savez_compressed(path, **{k: np.ascontiguousarray(v) for k, v in out.items()})
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB", len(out), "arrays")
+    import scenes  # tests/golden/scenes.py: fixture sets stored in parts of under 1 MiB
+    paths = scenes.save_parts(os.path.join(HERE, "tiny_scene"), {k: np.ascontiguousarray(v) for k, v in out.items()})
+    print("wrote", paths, sum(os.path.getsize(p) for p in paths) // 1024, "KiB", len(out), "arrays")
 
     # room0-shape case: inputs regenerated from seeds by the oracle; outputs + grad norms stored
     room = room0_case()

@@ -192,8 +192,7 @@ def quat_from_c2w(RT):
 
 
 def tiny_inputs():
-    with np.load(os.path.join(HERE, "tiny_scene.npz")) as z:
-        tiny = {k: z[k] for k in z.files}
+    tiny = scenes.load_parts(os.path.join(HERE, "tiny_scene"))
     bound = torch.from_numpy(tiny["bound"])
     b2, _, _ = scenes.tiny_window()
     assert np.array_equal(b2, tiny["bound"]), (b2, tiny["bound"])
@@ -476,9 +475,9 @@ def main():
     out.update(np_dict("map.", mapper_loop_case()))
     out.update(np_dict("frustum.", frustum_case()))
     out.update(np_dict("overlap.", overlap_case()))
-    path = os.path.join(HERE, "loop_fixtures.npz")
-    np.savez_compressed(path, **{k: (np.ascontiguousarray(v) if np.ndim(v) else np.asarray(v)) for k, v in out.items()})
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB", len(out), "arrays")
+    paths = scenes.save_parts(os.path.join(HERE, "loop_fixtures"),
+                              {k: (np.ascontiguousarray(v) if np.ndim(v) else np.asarray(v)) for k, v in out.items()})
+    print("wrote", paths, sum(os.path.getsize(p) for p in paths) // 1024, "KiB", len(out), "arrays")
     print("map losses", out["map.losses"], "selected", out["map.selected"])
     print("track losses", out["track.losses"])
     print("overlap scores", out["overlap.scores"], "selected", out["overlap.selected"])

@@ -13,6 +13,44 @@ ROOM0_BOUND = [[-2.9, 8.9], [-3.2, 5.5], [-3.5, 3.3]]       # configs/Replica/ro
 ROOM0_CAM = dict(H=680, W=1200, fx=600.0, fy=600.0, cx=599.5, cy=339.5)  # configs/Replica/replica.yaml
 TINY_BOUND = [[0.0, 3.0], [-0.5, 2.2], [0.2, 2.5]]           # tests/golden/make_golden.py (tiny_scene.npz)
 TINY_CAM = dict(H=96, W=128, fx=60.0, fy=60.0, cx=63.5, cy=47.5)
+PART_BYTES = 900 * 1024  # every committed fixture file stays under 1 MiB
+
+
+def save_parts(stem, arrays):
+    """np.savez_compressed of `arrays` over stem.0.npz, stem.1.npz, ...: consecutive entries per file,
+    a new file whenever the (zlib-estimated) size would pass PART_BYTES.  Returns the paths written."""
+    import glob
+    import os
+    import zlib
+    for old in glob.glob(glob.escape(stem) + ".*.npz"):
+        os.remove(old)
+    parts, size = [{}], 0
+    for k, v in arrays.items():
+        n = len(zlib.compress(np.ascontiguousarray(v).tobytes())) + 256 + 2 * len(k)
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += n
+    paths = []
+    for i, p in enumerate(parts):
+        paths.append(f"{stem}.{i}.npz")
+        np.savez_compressed(paths[-1], **p)
+        assert os.path.getsize(paths[-1]) < 1 << 20, paths[-1]
+    return paths
+
+
+def load_parts(stem):
+    """The arrays of every stem.<i>.npz (save_parts) as one dict."""
+    import glob
+    paths = sorted(glob.glob(glob.escape(stem) + ".*.npz"), key=lambda p: int(p.rsplit(".", 2)[1]))
+    if not paths:
+        raise FileNotFoundError(stem + ".*.npz")
+    out = {}
+    for p in paths:
+        with np.load(p) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def look_pose(center, yaw, pitch, offset=(0.0, 0.0, 0.0)):

@@ -15,7 +15,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from conftest import GOLDEN, REPO
+from conftest import REPO, load_golden
 
 
 def _free_port():
@@ -43,8 +43,7 @@ def _worker(rank, world, port, out_path):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     torch.set_num_threads(2)
     D = importlib.import_module("nice-slam_amd").distributed
-    with np.load(os.path.join(GOLDEN, "tiny_scene.npz")) as z:
-        t = {k: z[k] for k in z.files}
+    t = load_golden("tiny_scene")
     bound = torch.from_numpy(t["bound"])
     sd = {k[3:]: torch.from_numpy(v).clone().requires_grad_(k.startswith("sd.color_decoder"))
           for k, v in t.items() if k.startswith("sd.")}
@@ -248,8 +247,7 @@ def _sharded_setup(rank):
     import sys
     sys.path.insert(0, REPO)
     P = importlib.import_module("nice-slam_amd")
-    with np.load(os.path.join(GOLDEN, "tiny_scene.npz")) as z:
-        t = {k: z[k] for k in z.files}
+    t = load_golden("tiny_scene")
     bound = torch.from_numpy(t["bound"])
     sd = {k[3:]: torch.from_numpy(v) for k, v in t.items() if k.startswith("sd.") and not k.startswith("sd.coarse")}
     nice = P.NICE(c_dim=32, coarse=False, middle_grid_len=0.64, fine_grid_len=0.32, color_grid_len=0.32)

@@ -22,7 +22,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from conftest import GOLDEN, REPO
+from conftest import GOLDEN, REPO, load_golden
 
 pytestmark = pytest.mark.gpu
 N_PER, ITERS, SEED = 150, 3, 11
@@ -47,8 +47,7 @@ def _run(world, rank, group=None, mode="allreduce", force=False, graph=False):
     P = importlib.import_module("nice-slam_amd")
     import scenes
     dev = torch.device("cuda:0")
-    with np.load(os.path.join(GOLDEN, "tiny_scene.npz")) as z:
-        t = {k: z[k] for k in z.files}
+    t = load_golden("tiny_scene")
     bound = torch.from_numpy(t["bound"])
     sd = {k[3:]: torch.from_numpy(v) for k, v in t.items() if k.startswith("sd.") and not k.startswith("sd.coarse")}
     nice = P.NICE(c_dim=32, coarse=False, middle_grid_len=0.64, fine_grid_len=0.32, color_grid_len=0.32)
@@ -128,8 +127,8 @@ def test_two_rank_sharded_engine_matches_single_rank(tmp_path, mode):
         if k != "losses":
             assert torch.equal(r0[k], r1[k]), k   # identical summed gradients / all-gathered updates
     full = _run(1, 0)
-    with np.load(os.path.join(GOLDEN, "tiny_scene.npz")) as z:
-        start = {k: torch.from_numpy(z[k]) for k in ("grid_middle", "grid_fine", "grid_color")}
+    z = load_golden("tiny_scene")
+    start = {k: torch.from_numpy(z[k]) for k in ("grid_middle", "grid_fine", "grid_color")}
     # per-rank losses are shard sums: together they are the full batch's loss
     np.testing.assert_allclose((r0["losses"] + r1["losses"]).numpy(), full["losses"].numpy(), rtol=1e-5)
     for k, s in start.items():
@@ -167,8 +166,8 @@ def test_world1_rccl_exchange_in_hipgraph_is_identity(tmp_path, mode):
     r = torch.load(tmp_path / "rccl1.pt", weights_only=True)
     assert bool(r.pop("backend"))
     ref = _run(1, 0, graph=True)
-    with np.load(os.path.join(GOLDEN, "tiny_scene.npz")) as z:
-        start = {k: torch.from_numpy(z[k]) for k in ("grid_middle", "grid_fine", "grid_color")}
+    z = load_golden("tiny_scene")
+    start = {k: torch.from_numpy(z[k]) for k in ("grid_middle", "grid_fine", "grid_color")}
     np.testing.assert_allclose(r["losses"].numpy(), ref["losses"].numpy(), rtol=1e-6)
     for k, s0 in start.items():
         d, d_ref = r[k] - s0, ref[k] - s0

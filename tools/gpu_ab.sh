@@ -12,7 +12,7 @@ import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')
 for r in $(seq 1 ${ROUNDS:-1}); do
   for L in "$@"; do
     n=$(basename $L .so)
-    NSLAM_LIB=$PWD/$L timeout -k 10 300 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-stress --no-bulk --no-frames > $OUT/bench_${n}_$r.json 2> $OUT/bench_$n.err || { tail -20 $OUT/bench_$n.err; exit 1; }
+    NSLAM_LIB=$PWD/$L timeout -k 10 300 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-stress --no-bulk --no-frames > $OUT/bench_${n}_$r.json 2> $OUT/bench_$n.err || { tail -20 $OUT/bench_$n.err; exit 1; }
     summ $OUT/bench_${n}_$r.json "$n round $r"
   done
 done
@@ -30,6 +30,6 @@ PY
 [ -n "$NO_TRACE" ] && exit 0
 for L in "$@"; do
   n=$(basename $L .so)
-  NSLAM_LIB=$PWD/$L timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_$n -o run -- python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-stress --no-frames --no-bulk > $OUT/trace_$n.log 2>&1 || { tail -20 $OUT/trace_$n.log; exit 1; }
+  NSLAM_LIB=$PWD/$L timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_$n -o run -- python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-stress --no-frames --no-bulk > $OUT/trace_$n.log 2>&1 || { tail -20 $OUT/trace_$n.log; exit 1; }
   python tools/timeline.py $OUT/trace_$n/run_kernel_trace.csv 7 > $OUT/timeline_$n.txt && echo "== $n" && cat $OUT/timeline_$n.txt
 done

@@ -13,8 +13,7 @@ sys.path.insert(0, REPO)
 import conftest  # noqa: E402
 import test_gpu_fused as T  # noqa: E402
 
-with np.load(os.path.join(conftest.GOLDEN, "tiny_scene.npz")) as z:
-    tiny = {k: z[k] for k in z.files}
+tiny = conftest.load_golden("tiny_scene")
 sc, frames = T._frames(tiny)
 nice, c = T._nice(sc)
 eng = T.P.engine.MappingEngine(nice, c, sc.bound, 32, 16, device=T.DEV)
