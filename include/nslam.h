@@ -442,6 +442,61 @@ int nslam_cam_vector_batch(const float* c2w, int64_t c2w_stride, int32_t n, floa
  * reference to within ~1 ulp per entry (bit-identical for most poses), not bit-for-bit. */
 int nslam_cam_pose(const float* cam, float* c2w, void* stream);
 
+/* Mesh extraction (Mesher.get_mesh, src/utils/Mesher.py); additive, no ABI bump.
+ *
+ * Seen / forecast / unseen masks of n points (float32 [n][3]) against n_frames keyframes (Mesher.py:53-212).
+ * w2c: device float32 [n_frames][16], row-major world-to-camera matrices (inverted by the caller on the
+ * host, as the reference does).  depth: device float32 [n_frames][H][W] (may be NULL with use_all_frames,
+ * which reads no depth).  Per point and keyframe, in float32 without FMA contraction: cam = w2c . [p, 1]
+ * (four products summed left to right), cam.x negated, uv = K . cam, z = uv.z + 1e-8, uv /= z;
+ * seen: 0 < u < W, 0 < v < H, z < 0; forecast: the same with the image grown by 1000 pixels per side.
+ * depth_test: the depth is sampled at uv as F.grid_sample does (bilinear, zero padding, align_corners) and
+ * seen also needs |(-cam.z) - sample| < 2.4, forecast -cam.z < the maximum sample over ALL points of the
+ * chunk of points_batch_size points the point lies in (one maximum per chunk and keyframe, Mesher.py:166).
+ * Without depth_test both need -cam.z < max(depth) * 1.1.  forecast &= ~seen, unseen = neither; the three
+ * outputs are uint8 [n].  ws: the size function's bytes (the per-chunk maxima). */
+int nslam_point_masks(const float* pts, int64_t n, const float* w2c, int32_t n_frames, const float* depth, int32_t H,
+                      int32_t W, float fx, float fy, float cx, float cy, int32_t depth_test, int32_t use_all_frames,
+                      int64_t points_batch_size, uint8_t* seen, uint8_t* forecast, uint8_t* unseen, void* ws,
+                      size_t ws_bytes, void* stream);
+size_t nslam_point_masks_workspace_size(int64_t n, int32_t n_frames, int64_t points_batch_size);
+
+/* Marching cubes of vol (device float32 [nx][ny][nz], z fastest) at `level`.  An edge crosses when
+ * (a < level) != (b < level); every lattice point owns its +x, +y and +z edges.
+ * Pass 1 writes into ws (the size function's bytes = 4 nx ny nz): flags uint8 [N][3] (the owned edge
+ * crosses), then ntri uint8 [N] (triangles of the cell whose low corner the point is).  The caller turns both
+ * into exclusive int32 prefix sums vert_off [N][3] and face_off [N]; their totals are n_verts and n_faces.
+ * Pass 2 writes verts float64 [n_verts][3] = origin + (index + t) * spacing with t = (level - a) / (b - a) in
+ * float32 along the crossing edge, and faces int32 [n_faces][3] (vertex ids), vertices in owner-edge order,
+ * faces in cell order.  Face normals (right-hand rule) point toward decreasing field values.  The case
+ * table is csrc/nslam_mc_table.h (tools/gen_mc_table.py).  NSLAM_EUNSUPPORTED when 3 N >= 2^31. */
+int nslam_mc_count(const float* vol, int32_t nx, int32_t ny, int32_t nz, float level, void* ws, size_t ws_bytes,
+                   void* stream);
+int nslam_mc_emit(const float* vol, int32_t nx, int32_t ny, int32_t nz, float level, const double* origin,
+                  const double* spacing, const int32_t* vert_off, const int32_t* face_off, int64_t n_verts,
+                  int64_t n_faces, double* verts, int32_t* faces, void* stream);
+size_t nslam_mc_workspace_size(int32_t nx, int32_t ny, int32_t nz);
+
+/* inside[i] = 1 when planes[k] . (p_i, 1) <= 0 for every k (planes: device float64 [m][4], outward
+ * normals); pts is float64 [n][3] when is_double, else float32. */
+int nslam_points_in_hull(const void* pts, int32_t is_double, int64_t n, const double* planes, int32_t m,
+                         uint8_t* inside, void* stream);
+/* keep[f] = 0 when all three vertices of face f have vmask set, else 1. */
+int nslam_mesh_face_cull(const int32_t* faces, int64_t n_faces, const uint8_t* vmask, int64_t n_verts, uint8_t* keep,
+                         void* stream);
+/* Connected components over shared vertices: label int32 [n_verts] = the smallest vertex id of the
+ * vertex's component (hook and compress, repeated until the device word `flag` stays clear; synchronises the
+ * stream once per round); area float64 [n_verts]: area[l] = the summed triangle area of component l (atomic
+ * float64 sums: the last bits vary from run to run), 0 elsewhere. */
+int nslam_mesh_components(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int32_t* label,
+                          double* area, int32_t* flag, void* stream);
+/* keep[f] = the face's component is *largest (device int64; NULL = unused) or has area > threshold;
+ * used[v] = 1 for every vertex of a kept face (the caller zeroes used). */
+int nslam_mesh_select(const int32_t* faces, int64_t n_faces, const int32_t* label, const double* area,
+                      const int64_t* largest, double threshold, uint8_t* keep, uint8_t* used, void* stream);
+/* out[f][c] = new_id[faces[f][c]]. */
+int nslam_mesh_remap(const int32_t* faces, int64_t n_faces, const int32_t* new_id, int32_t* out, void* stream);
+
 enum { NSLAM_WS_SAMPLER = 0 };
 size_t nslam_workspace_size(int which, int64_t n);
 

@@ -129,6 +129,10 @@ EXPORTS = (
     "nslam_query_tape_size", "nslam_color_wgrad", "nslam_cam_grad_parts", "nslam_cam_grad_batch",
     "nslam_cam_pose_batch", "nslam_frustum_rows", "nslam_frustum_rows_workspace_size", "nslam_track_best",
     "nslam_loss_sum_best", "nslam_cam_vector_batch", "nslam_cam_grad_step",
+    # mesh extraction (additive: no ABI bump)
+    "nslam_point_masks", "nslam_point_masks_workspace_size", "nslam_mc_count", "nslam_mc_emit",
+    "nslam_mc_workspace_size", "nslam_points_in_hull", "nslam_mesh_face_cull", "nslam_mesh_components",
+    "nslam_mesh_select", "nslam_mesh_remap",
 )
 
 _lib = None
@@ -201,6 +205,20 @@ def lib():
         L.nslam_cam_vector_batch.argtypes = [vp, i64, i32, vp, vp, vp]
         L.nslam_cam_grad_step.argtypes = [ctypes.POINTER(NslamCamTail), vp, ctypes.POINTER(vp), i32, vp, vp, i64, i32,
                                           vp, vp, vp, vp]
+        f64 = ctypes.c_double
+        L.nslam_point_masks.argtypes = [vp, i64, vp, i32, vp, i32, i32, f32, f32, f32, f32, i32, i32, i64, vp, vp, vp,
+                                        vp, sz, vp]
+        L.nslam_point_masks_workspace_size.argtypes = [i64, i32, i64]
+        L.nslam_point_masks_workspace_size.restype = sz
+        L.nslam_mc_count.argtypes = [vp, i32, i32, i32, f32, vp, sz, vp]
+        L.nslam_mc_emit.argtypes = [vp, i32, i32, i32, f32, dp, dp, vp, vp, i64, i64, vp, vp, vp]
+        L.nslam_mc_workspace_size.argtypes = [i32, i32, i32]
+        L.nslam_mc_workspace_size.restype = sz
+        L.nslam_points_in_hull.argtypes = [vp, i32, i64, vp, i32, vp, vp]
+        L.nslam_mesh_face_cull.argtypes = [vp, i64, vp, i64, vp, vp]
+        L.nslam_mesh_components.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp]
+        L.nslam_mesh_select.argtypes = [vp, i64, vp, vp, vp, f64, vp, vp, vp]
+        L.nslam_mesh_remap.argtypes = [vp, i64, vp, vp, vp]
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L

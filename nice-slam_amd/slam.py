@@ -96,3 +96,9 @@ class SlamState:
         self.output = cfg.get("data", {}).get("output", "output")
         from .renderer import Renderer
         self.renderer = Renderer(cfg, None, self)
+        # the mesher reads cfg['meshing'] and cfg['mapping']['marching_cubes_bound']; configs without them
+        # (hot-path-only runs) get none
+        self.mesher = None
+        if "meshing" in cfg and "marching_cubes_bound" in cfg.get("mapping", {}) and "scale" in cfg:
+            from .mesher import Mesher
+            self.mesher = Mesher(cfg, None, self)
