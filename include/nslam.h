@@ -181,6 +181,34 @@ size_t nslam_query_tape_size(int64_t n_pts); /* ABI v9 */
  * Tracker.optimize_cam_in_batch's backward (Tracker.py:125) / Mapper.optimize_map's (Mapper.py:503). */
 int nslam_query_bwd_decoders(const nslam_query_cfg* cfg, int32_t dec_mask, const double* pts, int64_t n_pts,
                              const float* g_raw, double* const* g_pts, void* stream);
+/* Live-point lists (additive, no ABI bump).  With a frustum-compacted grid gradient (nslam_grid.slot) a
+ * mapping backward without d/dpts has one output per decoder: the scatter into the selected rows.  A point
+ * whose 8 corner rows of grid[d] all have slot < 0 contributes nothing (the reference never forms those
+ * gradients, Mapper.py:314-333,394-401), yet nslam_query_bwd_decoders runs its whole cotangent chain and
+ * scatter walk.  For every decoder d in dec_mask (bit d), nslam_live_points writes live_idx[d] (device int32,
+ * capacity n_pts): the indices, ascending, of the valid points with at least one corner row of grid[d] whose
+ * slot >= 0 — the corners are formed by the query kernels' own arithmetic, so the list is exactly what the
+ * scatter would keep — and *n_live[d] (device int64) = their count.  A grid without a slot map keeps every
+ * point.  live_idx / n_live: HOST arrays of 4 device pointers, indexed by NSLAM_DEC_*.  Three launches
+ * (flags + per-block counts, a scan of the counts, the indices), deterministic; nothing of the iteration's
+ * map state is read but the slot maps, so with the rays of a batch known the lists can be formed ahead of
+ * the backward on another stream.  A list is valid for the slot maps it was formed from: after a slot map
+ * is rewritten the lists are formed again.  ws: nslam_live_points_workspace_size(n_pts) bytes, 8-byte
+ * aligned.  n_pts < 2^31. */
+int nslam_live_points(const nslam_query_cfg* cfg, int32_t dec_mask, const double* pts, int64_t n_pts,
+                      int32_t* const* live_idx, int64_t* const* n_live, void* ws, size_t ws_bytes, void* stream);
+size_t nslam_live_points_workspace_size(int64_t n_pts);
+/* nslam_query_bwd_decoders over each decoder's live points only: lane p of 32-point tile t of decoder d
+ * takes point live_idx[d][32 t + p] (its point, cotangent row and ReLU masks are gathered by that index);
+ * lanes at or past *n_live[d] write nothing.  The launch is sized for n_pts points whatever the lists hold
+ * (workgroups past a list's end exit at once), so a captured hipGraph stays valid for later lists.  The grid
+ * gradients equal nslam_query_bwd_decoders' up to the order of their float atomics: each point's cotangent
+ * is computed independently of the tile it sits in, only the runs of equal voxels merged before the atomics
+ * regroup.  cfg->need_pts_grad is NSLAM_EUNSUPPORTED (d/dpts is needed for every point); otherwise the
+ * requirements of nslam_query_bwd_decoders. */
+int nslam_query_bwd_decoders_live(const nslam_query_cfg* cfg, int32_t dec_mask, const double* pts, int64_t n_pts,
+                                  const float* g_raw, const int32_t* const* live_idx, const int64_t* const* n_live,
+                                  void* stream);
 /* ABI v16: the colour decoder's parameter gradients of a colour-stage backward (added into
  * cfg->dgrad[COLOR]; Mapper.py:503 for color_decoder.parameters(), decoder.py:177-203) from the
  * forward's activation tape and ReLU masks (cfg->act_tape, cfg->saved_masks) and the cotangent

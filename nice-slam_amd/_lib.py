@@ -133,6 +133,8 @@ EXPORTS = (
     "nslam_point_masks", "nslam_point_masks_workspace_size", "nslam_mc_count", "nslam_mc_emit",
     "nslam_mc_workspace_size", "nslam_points_in_hull", "nslam_mesh_face_cull", "nslam_mesh_components",
     "nslam_mesh_select", "nslam_mesh_remap",
+    # live-point lists of the mask-only mapping backward (additive: no ABI bump)
+    "nslam_live_points", "nslam_live_points_workspace_size", "nslam_query_bwd_decoders_live",
 )
 
 _lib = None
@@ -219,6 +221,12 @@ def lib():
         L.nslam_mesh_components.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp]
         L.nslam_mesh_select.argtypes = [vp, i64, vp, vp, vp, f64, vp, vp, vp]
         L.nslam_mesh_remap.argtypes = [vp, i64, vp, vp, vp]
+        L.nslam_live_points.argtypes = [ctypes.POINTER(NslamQueryCfg), i32, vp, i64, ctypes.POINTER(vp),
+                                        ctypes.POINTER(vp), vp, sz, vp]
+        L.nslam_live_points_workspace_size.argtypes = [i64]
+        L.nslam_live_points_workspace_size.restype = sz
+        L.nslam_query_bwd_decoders_live.argtypes = [ctypes.POINTER(NslamQueryCfg), i32, vp, i64, vp,
+                                                    ctypes.POINTER(vp), ctypes.POINTER(vp), vp]
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L

@@ -354,6 +354,13 @@ __device__ __forceinline__ void load_masks(const QueryKArgs& a, int dec, int64_t
 #pragma unroll
   for (int i = 0; i < 5; ++i) m[i] = s[i * 64 + lane];
 }
+// The masks of point idx, lane half h, wherever the forward's tiling put them (a live-point tile gathers
+// its points from many source tiles): a per-lane tile and lane instead of the wave's.
+__device__ __forceinline__ void load_masks_at(const QueryKArgs& a, int dec, int64_t idx, int h, uint32_t m[5]) {
+  const uint16_t* s = mask_slot(a, dec, idx >> 5) + ((int)(idx & 31) | (h << 5));
+#pragma unroll
+  for (int i = 0; i < 5; ++i) m[i] = s[i * 64];
+}
 
 // Activation tape of the colour decoder (ABI v9 nslam_query_cfg.act_tape): the forward stores the
 // post-ReLU hidden tiles h0..h4 of every tile (C layout) and the weight-gradient backward reads them
@@ -1922,9 +1929,15 @@ constexpr int bwd_scratch_floats(int WG, bool PG, bool SAVED) {
   return WG ? kScratchFloats : lean_tr(WG, PG, SAVED) ? kWalkFloats : TILE_FLOATS + kWalkFloats;
 }
 
-template <int DEC, int WG, bool PG, bool FIRST, bool SAVED>
+// LIVE (mask-only mapping tiles): lane p of tile t takes point live[32 t + p] of the decoder's live-point
+// list (nslam_live_points: the points with a frustum-selected corner, ascending), nlive entries; lanes past
+// the list behave like tail lanes.  Each point's cotangent is its own MFMA column, so it does not depend
+// on the tile the point sits in; only the runs the scatter walk merges before its atomics regroup.
+template <int DEC, int WG, bool PG, bool FIRST, bool SAVED, bool LIVE = false>
 __device__ __forceinline__ void dec_bwd_tile(const QueryKArgs& a, int64_t tile, const Slab& A, const Scratch& S,
-                                             int lane, double* __restrict__ gpts, int64_t gbase = 0) {
+                                             int lane, double* __restrict__ gpts, int64_t gbase = 0,
+                                             const int32_t* __restrict__ live = nullptr, int64_t nlive = 0) {
+  static_assert(!LIVE || (SAVED && WG == 0 && !PG), "live-point tiles: the mask-only mapping backward");
   // gpts: d/dpts of point idx at gpts[(idx - gbase) * 3 + k] (gbase: a tile's LDS staging rows)
   // Every scratch / slab address is a function of the lane only, i.e. invariant across the tile
   // loop; letting LICM hoist the ~300 of them pins (and spills) the register file.  Re-derive
@@ -1932,7 +1945,11 @@ __device__ __forceinline__ void dec_bwd_tile(const QueryKArgs& a, int64_t tile, 
   asm volatile("" : "+v"(lane));
   PHASE(DEC, 0);
   const int h = lane >> 5, p = lane & 31;
-  const int64_t idx = tile * 32 + p;
+  int64_t idx = tile * 32 + p;
+  if (LIVE) {  // (a.n: an invalid lane; so is an entry that is no point index, whatever the list holds)
+    const uint32_t v = idx < nlive ? (uint32_t)live[idx] : 0xffffffffu;
+    idx = (int64_t)v < a.n ? (int64_t)v : a.n;
+  }
   const Pt q = load_point(a, idx);
   float g[4] = {0.f, 0.f, 0.f, 0.f};
   if (q.valid) {
@@ -1977,7 +1994,10 @@ __device__ __forceinline__ void dec_bwd_tile(const QueryKArgs& a, int64_t tile, 
   float* const img = IMGDC ? S.sA : nullptr;
   if (SAVED) {  // masks from the forward: no recompute (the mask-only chain)
     uint32_t m[5];
-    load_masks(a, DEC, tile, m, lane);
+    if (LIVE)
+      load_masks_at(a, DEC, q.valid ? idx : 0, h, m);
+    else
+      load_masks(a, DEC, tile, m, lane);
     // the walk table goes to LDS before the chain (its corner rows and weights need no registers
     // through it); the slot loads were issued before the masks, so this waits for nothing extra
     if (WG == 0 && gr.grad) stage_walk_table(tab, scn, cr.cell, lane);
@@ -2103,6 +2123,9 @@ struct MultiDecArgs {
   int ndec;
   int dec[4];
   double* gp[4];
+  // LIVE launches (nslam_query_bwd_decoders_live): each part's live-point list and its device length
+  const int32_t* live[4];
+  const int64_t* nlive[4];
 };
 // (a colour decoder with weight gradients runs here as its lean chain too: grid gradient, d/dpts;
 // its parameter gradients come from k_color_wgrad, nslam_color_wgrad.hip)
@@ -2117,8 +2140,11 @@ struct MultiDecArgs {
 #define NSLAM_MULTI_PG_LB 3  // the d/dpts (tracking, bundle adjustment) variant: 163 VGPRs with dc in the
                              // scatter image through the Fourier backward (218 before: 2 waves/SIMD)
 #endif
-template <bool PG>
+// LIVE: the grid is sized for every point (a captured launch stays valid whatever the lists hold); a wave
+// whose tile lies past its part's list exits at once.
+template <bool PG, bool LIVE = false>
 __global__ __launch_bounds__(64 * kWavesBwd, PG ? NSLAM_MULTI_PG_LB : NSLAM_MULTI_LB) void k_dec_bwd_multi(QueryKArgs a, MultiDecArgs m) {
+  static_assert(!(PG && LIVE), "d/dpts is needed for every point");
   constexpr int kScr = bwd_scratch_floats(0, PG, true);
   __shared__ __attribute__((aligned(16))) float lds[kWavesBwd * kScr];
   const int lane = threadIdx.x & 63, wave = wave_id();
@@ -2131,15 +2157,29 @@ __global__ __launch_bounds__(64 * kWavesBwd, PG ? NSLAM_MULTI_PG_LB : NSLAM_MULT
   const int dec = part == 0 ? m.dec[0] : part == 1 ? m.dec[1] : part == 2 ? m.dec[2] : m.dec[3];
   double* gp = part == 0 ? m.gp[0] : part == 1 ? m.gp[1] : part == 2 ? m.gp[2] : m.gp[3];
   const int64_t w = (int64_t)(blockIdx.x / (unsigned)m.ndec) * kWavesBwd + wave;
-  const int64_t ntiles = (a.n + 31) / 32;
+  const int32_t* live = nullptr;
+  int64_t nlive = a.n;
+  if (LIVE) {
+    live = part == 0 ? m.live[0] : part == 1 ? m.live[1] : part == 2 ? m.live[2] : m.live[3];
+    const int64_t* np = part == 0 ? m.nlive[0] : part == 1 ? m.nlive[1] : part == 2 ? m.nlive[2] : m.nlive[3];
+    nlive = *np;
+    if (nlive > a.n) nlive = a.n;  // (never more entries than the list's capacity)
+  }
+  const int64_t ntiles = (nlive + 31) / 32;
   if (w >= ntiles) return;
   TL(1, 0, part);
   const Slab A = make_slab(nullptr, 0);
   switch (dec) {
-    case NSLAM_DEC_COARSE: dec_bwd_tile<NSLAM_DEC_COARSE, 0, PG, true, true>(a, w, A, S, lane, gp); break;
-    case NSLAM_DEC_MIDDLE: dec_bwd_tile<NSLAM_DEC_MIDDLE, 0, PG, true, true>(a, w, A, S, lane, gp); break;
-    case NSLAM_DEC_FINE: dec_bwd_tile<NSLAM_DEC_FINE, 0, PG, true, true>(a, w, A, S, lane, gp); break;
-    default: dec_bwd_tile<NSLAM_DEC_COLOR, 0, PG, true, true>(a, w, A, S, lane, gp); break;
+    case NSLAM_DEC_COARSE:
+      dec_bwd_tile<NSLAM_DEC_COARSE, 0, PG, true, true, LIVE>(a, w, A, S, lane, gp, 0, live, nlive);
+      break;
+    case NSLAM_DEC_MIDDLE:
+      dec_bwd_tile<NSLAM_DEC_MIDDLE, 0, PG, true, true, LIVE>(a, w, A, S, lane, gp, 0, live, nlive);
+      break;
+    case NSLAM_DEC_FINE:
+      dec_bwd_tile<NSLAM_DEC_FINE, 0, PG, true, true, LIVE>(a, w, A, S, lane, gp, 0, live, nlive);
+      break;
+    default: dec_bwd_tile<NSLAM_DEC_COLOR, 0, PG, true, true, LIVE>(a, w, A, S, lane, gp, 0, live, nlive); break;
   }
   TL(1, 1, 0);
 }

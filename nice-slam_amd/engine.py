@@ -107,6 +107,7 @@ class MappingEngine:
         self._pre = None     # (key, [buffer set 0, buffer set 1]) ray batches of the prefetch loop
         self._parity = 0     # which set holds this iteration's batch
         self._pre_stream = None
+        self._live_gen = [None, None]  # (layout_gen, rows_gen) each buffer set's live-point lists were formed at
         self._side = []     # side streams of the concurrent decoder backward
         self.concurrent = True
         # concurrent backward: enqueue the colour weight-gradient branch before the grid-gradient one
@@ -132,6 +133,14 @@ class MappingEngine:
         # main stream after the join ("main", experiment)
         self.adam_on = _env_choice("NSLAM_ADAM_ON", "side", ("side", "main"))
         self._wg_ev = None
+        # live-point lists (nslam_live_points): the mask-only backward of a mapping iteration without d/dpts
+        # runs only the points that touch a frustum-selected voxel of the decoder's grid — with compacted
+        # grid gradients the others add nothing.  The lists belong to the ray batch: iteration() forms them
+        # right after the sampler (with prefetch: an iteration ahead, on the side stream).  0: every point,
+        # as nslam_query_bwd_decoders.  Measured on the synthetic room0 window only (about half of the kept
+        # points are dead there); the dead share of a real sequence has not been measured.
+        self.live_points = _env_choice("NSLAM_LIVE_POINTS", "1", ("0", "1")) == "1"
+        self.rows_gen = 0  # bumped whenever a slot map is rewritten in place (bind_masks, Mapper._bind_frustum)
         for k, v in c.items():
             if not v.is_contiguous(memory_format=torch.channels_last_3d):
                 raise ValueError(f"{k} must be channels-last (ops.channels_last)")
@@ -225,6 +234,7 @@ class MappingEngine:
             self._cap_keys = keys
             self.gall.zero_()
             self._clean = True
+        self.rows_gen += 1  # live-point lists formed from the old slot maps are stale
         for k in keys:
             full, n_live, ar = self._cap[k]
             n = ar.numel()
@@ -264,6 +274,38 @@ class MappingEngine:
         cfg.act_tape = ptr(self._tape)
         return cfg
 
+    def live_lists(self, stage, ro, rd, z, out=None):
+        """(live_idx int32 [decoders of the stage, N*S], n_live int64 [4, by NSLAM_DEC_*]) of a ray batch
+        against the current slot maps (nslam_live_points), on the current stream: per decoder the ascending
+        indices of the points with a frustum-selected corner in its grid and their count.  Valid until a
+        slot map changes (set_rows, bind_masks).  out: (live_idx, n_live) to write into."""
+        decs = ops._DEC_FOR_STAGE[stage]
+        n = z.numel()
+        if out is None:
+            out = (torch.empty(len(decs), n, dtype=torch.int32, device=z.device),
+                   torch.zeros(4, dtype=torch.int64, device=z.device))
+        idx, nl = out
+        keys = tuple(_GRID_OF[d] for d in decs) if self.grid_grads else ()
+        saved, tape = self._saved, self._tape
+        self._saved = self._tape = None  # (the lists need neither)
+        try:
+            cfg = self._cfg(stage, ro, rd, z, keys, ())
+        finally:
+            self._saved, self._tape = saved, tape
+        ips, nps = (ctypes.c_void_p * 4)(), (ctypes.c_void_p * 4)()
+        mask = 0
+        for i, name in enumerate(decs):
+            d = ops._DEC_ID[name]
+            mask |= 1 << d
+            ips[d] = idx[i].data_ptr()
+            nps[d] = nl[d:d + 1].data_ptr()
+        wsb = lib().nslam_live_points_workspace_size(n)
+        ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=z.device)
+        with ops._span("live_points"):
+            rc = lib().nslam_live_points(ctypes.byref(cfg), mask, None, n, ips, nps, ptr(ws), wsb, stream_ptr(z.device))
+        check(rc, "nslam_live_points")
+        return idx, nl
+
     def query_fwd(self, stage, ro, rd, z, defer_occ=False, tape=False):
         """raw [N*S, 4]; also saves the ReLU masks the backward of frozen decoders uses.
         defer_occ: raw[...,3] holds the fine occupancy only and self.occ_add the middle one (None
@@ -280,7 +322,7 @@ class MappingEngine:
         return raw
 
     def query_bwd(self, stage, ro, rd, z, g_raw, grid_grads, dec_grads, concurrent=None, pts_grad=False,
-                  on_branch=None, pts_parts=False, ordered_branches=False, on_pts=None):
+                  on_branch=None, pts_parts=False, ordered_branches=False, on_pts=None, live=None):
         """Backward into the engine's gradient buffers, as independent launches ("branches") that write
         disjoint buffers:
           lean     every decoder's grid gradient (and d/dpts) from the forward's ReLU masks, ONE launch
@@ -304,12 +346,17 @@ class MappingEngine:
         on_pts(parts): with pts_grad, called once every decoder's d/dpts share is written — on the lean
         launch's stream right after it when that launch forms all of them (bundle adjustment's camera
         gradient then runs beside the weight gradients, not after the join), else on the caller's stream
-        after the join."""
+        after the join.
+        live: live_lists() of this very batch and the current slot maps — the lean launch then runs each
+        decoder's live points only (nslam_query_bwd_decoders_live; ignored with pts_grad, which needs
+        every point)."""
         n = z.numel()
         self._clean = False
         concurrent = self.concurrent if concurrent is None else concurrent
         cfg = self._cfg(stage, ro, rd, z, grid_grads, dec_grads)
         cfg.need_pts_grad = int(bool(pts_grad))
+        if pts_grad:
+            live = None
         decs = list(ops._DEC_FOR_STAGE[stage])
         wgt = [d for d in decs if d in dec_grads]
         masks = self._saved is not None
@@ -343,7 +390,7 @@ class MappingEngine:
         with ops._span("query_bwd"):
             for st in used:  # fork: every branch starts from the same point of the main stream
                 st.wait_stream(main)
-                for t in (ro, rd, z, g_raw, self._saved, self._tape):
+                for t in (ro, rd, z, g_raw, self._saved, self._tape) + (tuple(live) if live else ()):
                     if t is not None:
                         t.record_stream(st)
             for i, (kind, names) in enumerate(units):
@@ -372,8 +419,17 @@ class MappingEngine:
                             if pts_grad:
                                 gps[d] = ptr(gp[name])
                         with ops._span("query_bwd." + "+".join(names)):
-                            rc = lib().nslam_query_bwd_decoders(ctypes.byref(lc), mask, None, n, ptr(g_raw), gps,
-                                                                st.cuda_stream)
+                            if live is not None:
+                                ips, nps = (ctypes.c_void_p * 4)(), (ctypes.c_void_p * 4)()
+                                for name in names:
+                                    d = ops._DEC_ID[name]
+                                    ips[d] = live[0][decs.index(name)].data_ptr()
+                                    nps[d] = live[1][d:d + 1].data_ptr()
+                                rc = lib().nslam_query_bwd_decoders_live(ctypes.byref(lc), mask, None, n, ptr(g_raw),
+                                                                         ips, nps, st.cuda_stream)
+                            else:
+                                rc = lib().nslam_query_bwd_decoders(ctypes.byref(lc), mask, None, n, ptr(g_raw),
+                                                                    gps, st.cuda_stream)
                         check(rc, "nslam_query_bwd_decoders")
                         if on_pts is not None and pts_grad and set(names) == set(decs):
                             for name in names:  # (allocated on the caller's stream)
@@ -497,6 +553,10 @@ class MappingEngine:
         next iteration by the join (it is: it runs on a stream the join covers).  Camera poses that a step changes in place make a prefetched batch
         stale (the version check cannot see a kernel's writes): the caller passes prefetch=False whenever
         its camera step can move them (Mapper: the colour stage, where their lr is not 0).
+        Live-point lists (self.live_points) ride with the batch and are formed again when a slot map was
+        rebound since (set_rows, bind_masks); a captured hipGraph of prefetching iterations replays the lists
+        of its capture-time ordering, so rebind rows only before a replay whose first iteration draws its
+        own batch (as Mapper.optimize_map's per-stage graphs do).
         """
         H, W = hw
         fx, fy, cx, cy = intrinsics
@@ -504,6 +564,10 @@ class MappingEngine:
         if exchange is not None and hasattr(exchange, "validate"):
             exchange.validate(self, keys, dnames)  # raises before anything of the iteration is enqueued
         draw = self.draws(seed, world, rank) if pix is None else None
+        # live-point lists: a mapping iteration without d/dpts whose grids (some of them) accumulate a
+        # frustum-compacted gradient; they ride with the ray batch (entries 6, 7 of a buffer set)
+        use_live = (self.live_points and post_bwd is None and self.grid_grads and self.merge
+                    and any(k in self.slot for k in keys))
 
         def rays(out=None):  # pixels → rays + inside mask, then the sampler (Mapper.py:457-484, Renderer.py:82-174)
             ro, rd, gd, gc, keep = ops.gather_rays(frames, pix, n_per, H, W, (0, H, 0, W), fx, fy, cx, cy,
@@ -518,7 +582,8 @@ class MappingEngine:
                 gm = gt_max(gd) if gt_max is not None else None
             z = ops.sample_z(ro, rd, gsamp, self.bound, self.n_strat, self.n_surf, self.lindisp, gt_max=gm,
                              out=None if out is None else out[5])
-            return [ro, rd, gd, gc, keep, z]
+            lv = list(self.live_lists(stage, ro, rd, z, out=None if out is None else out[6:8])) if use_live else []
+            return [ro, rd, gd, gc, keep, z] + lv
 
         prefetch = prefetch and pix is None
         side = None
@@ -527,7 +592,11 @@ class MappingEngine:
             # gathered from: held by weak reference (identity — a new tensor that reuses a freed one's
             # address is not the same frame) and version counter.
             ftens = [t for f in frames for t in f]
-            pkey = (stage, n_per, hw, use_gt_in_sampler, seed, world, rank)
+            pkey = (stage, n_per, hw, use_gt_in_sampler, seed, world, rank, use_live)
+            # live-point lists are valid for the slot maps they were formed from only: each buffer set
+            # remembers their generation (set_rows, bind_masks, Mapper._bind_frustum), and a set whose lists
+            # are older keeps its rays and gets new lists on the main stream before they are used
+            gen = (self.layout_gen, self.rows_gen)
             valid = (self._pre is not None and self._pre[0] == pkey and len(self._pre[1]) == len(ftens)
                      and all(r() is t and v == t._version for (r, v), t in zip(self._pre[1], ftens)))
             if not valid:
@@ -535,8 +604,14 @@ class MappingEngine:
                 self._pre = (pkey, [(weakref.ref(t), t._version) for t in ftens],
                              [first, [torch.empty_like(t) for t in first]])
                 self._parity = 0
-            cur, nxt = self._pre[2][self._parity], self._pre[2][1 - self._parity]
+                self._live_gen = [gen, None]
+            par = self._parity
+            cur, nxt = self._pre[2][par], self._pre[2][1 - par]
             self._parity ^= 1
+            if use_live and self._live_gen[par] != gen:
+                # (ordered after the side stream's writes of this set by the previous iteration's join)
+                self.live_lists(stage, cur[0], cur[1], cur[5], out=cur[6:8])
+                self._live_gen[par] = gen
             main = torch.cuda.current_stream(self.device)
             if self._pre_stream is None:
                 if self.prefetch_stream == "lean" and self.wgrad_first and self.concurrent:
@@ -555,12 +630,15 @@ class MappingEngine:
                 side.wait_stream(main)  # the previous iteration's backward has released `nxt`
                 with torch.cuda.stream(side):
                     rays(out=nxt)  # the next iteration's batch, beside this iteration's render + backward
+                self._live_gen[1 - par] = gen
 
             if self.prefetch_at == "start":
                 launch_prefetch()
-            ro, rd, gd, gc, keep, z = cur
+            batch = cur
         else:
-            ro, rd, gd, gc, keep, z = rays()
+            batch = rays()
+        ro, rd, gd, gc, keep, z = batch[:6]
+        live = tuple(batch[6:8]) if use_live else None
         mirror = hasattr(optimizer, "set_mirror")
         raw = self.query_fwd(stage, ro, rd, z, defer_occ=True, tape="color" in dnames)
         if side is not None and self.prefetch_at != "start":
@@ -602,7 +680,7 @@ class MappingEngine:
 
         on_pts = (lambda parts: post_bwd(parts, ro, rd, z)) if post_bwd is not None else None
         self.query_bwd(stage, ro, rd, z, g_raw, keys, dnames, on_branch=on_branch, ordered_branches=sharded,
-                       pts_grad=post_bwd is not None, pts_parts=True, on_pts=on_pts)
+                       pts_grad=post_bwd is not None, pts_parts=True, on_pts=on_pts, live=live)
         if sharded:
             pass
         elif exchange is not None:  # frustum-compacted all-reduce (distributed.SparseGradExchange)

@@ -361,6 +361,7 @@ class Mapper(object):
             return
         if getattr(eng, "_cap_keys", None) != tuple(sorted(keys)):
             eng.bind_masks({k: None for k in keys})  # (first call: the capacity buffers)
+        eng.rows_gen += 1  # the slot maps are rewritten in place: live-point lists formed from them are stale
         done = {}
         for k in keys:
             shp = tuple(self.c[k].shape[2:])
