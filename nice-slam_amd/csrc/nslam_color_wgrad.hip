@@ -29,7 +29,8 @@
 //                  row 3 is replaced by the stage combiner, decoder.py:341), dbo
 // Every role holds at most two weight blocks (the compiler keeps every role's loop-carried values live
 // in every wave, so the register budget is the union's).
-#include "nslam_query_impl.h"
+#include "nslam_query_core.h"
+#include "nslam_query_host.h"
 
 // k_color_wgrad asks for 4 waves per SIMD (launch bounds) to cap itself at 128 VGPRs, so two waves of
 // the lean backward fit beside its two on each SIMD; its 95 KiB of LDS keeps it at one workgroup per

@@ -394,30 +394,6 @@ __device__ __forceinline__ f32x16 gather_tile(const float* __restrict__ grid, co
   return acc;
 }
 
-// gather_tile with at most NB corners' loads in flight (a scheduling fence between batches): for a
-// gather whose result is only stored, in a kernel whose register budget is set elsewhere
-template <int NB>
-__device__ __forceinline__ f32x16 gather_tile_batched(const float* __restrict__ grid, const Corners& c, int lane) {
-  const int h = lane >> 5;
-  f32x16 acc = zero16();
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    if (k % NB == 0) __builtin_amdgcn_sched_barrier(0);
-    const gptr_t<f32x4> row = as_global(reinterpret_cast<const f32x4*>(grid + (size_t)c.row[k] * NSLAM_C_DIM + 4 * h));
-    const f32x4 v0 = row[0], v1 = row[2], v2 = row[4], v3 = row[6];
-    const float w = c.w[k];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      acc[j] += v0[j] * w;
-      acc[4 + j] += v1[j] * w;
-      acc[8 + j] += v2[j] * w;
-      acc[12 + j] += v3[j] * w;
-    }
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  return acc;
-}
-
 // d out / d (normalised coords) for cotangent tile g (this lane's 16 channels; caller adds the
 // other half with xor32 and multiplies by gmul)
 __device__ __forceinline__ void coord_grad_partial(const float* __restrict__ grid, const Corners& c,
@@ -504,7 +480,7 @@ __device__ __forceinline__ float fcos(float x) {
 // Adam element update (torch.optim.Adam single-tensor form, the reference's torch 1.11):
 //   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g g;  p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
 // with torch's GPU division by a host scalar done as a multiply by its float reciprocal.  Shared by
-// k_adam (nslam_mapping.hip) and the Adam epilogue of k_slab_reduce (nslam_query_impl.h).
+// k_adam (nslam_mapping.hip) and the Adam epilogue of k_slab_reduce (nslam_query.hip).
 // ------------------------------------------------------------------------------------------
 struct AdamCoef {
   float b1, omb1, b2, omb2, eps, rbc2s, step_size;

@@ -1,9 +1,11 @@
 // nslam_query.hip — C-ABI entry points of the fused point query (include/nslam.h): forward
-// launches, backward dispatch (the per-decoder backward launchers are compiled in
-// nslam_query_dec.hip), workspace / tape / mask sizes and the pack layout.
+// launches (the forward kernels: nslam_query_fwd.h), backward dispatch (the per-decoder backward
+// launchers are compiled in nslam_query_dec.hip), the slab reduction of the parameter gradients,
+// workspace / tape / mask sizes and the pack layout.
 #include <string.h>
 
-#include "nslam_query_impl.h"
+#include "nslam_query_fwd.h"
+#include "nslam_query_host.h"
 
 using namespace nslamq;
 
@@ -11,8 +13,7 @@ extern "C" int nslam_query_fwd(const nslam_query_cfg* cfg, const double* pts, in
                                void* stream) {
   const int rc = check_cfg(cfg, false);
   if (rc) return rc;
-  if (n_pts < 0 || (n_pts > 0 && ((!pts && !cfg->rays_o) || !raw))) return NSLAM_EINVAL;
-  if (cfg->rays_o && (n_pts >= (int64_t(1) << 31) || n_pts % cfg->n_samples)) return NSLAM_EINVAL;
+  if (check_points(cfg, pts, n_pts, raw != nullptr)) return NSLAM_EINVAL;
   if (n_pts == 0) return NSLAM_OK;
   QueryKArgs a{*cfg, pts, n_pts, raw, nullptr, nullptr};
   const int64_t tiles = (n_pts + 31) / 32;
@@ -29,8 +30,20 @@ extern "C" int nslam_query_fwd(const nslam_query_cfg* cfg, const double* pts, in
 
 extern "C" size_t nslam_query_fwd_workspace_size(const nslam_query_cfg* cfg, int64_t n_pts) {
   if (!cfg || n_pts <= 0 || cfg->stage < NSLAM_STAGE_FINE || cfg->stage > NSLAM_STAGE_COLOR) return 0;
-  return (((size_t)n_pts * sizeof(float) + 255) & ~(size_t)255) + 256;  // + the dynamic forward's counter
+  return (((size_t)n_pts * sizeof(float) + 255) & ~(size_t)255) + 256;  // the middle occupancy + 256 reserved
 }
+
+namespace {
+typedef void (*FwdKernel)(QueryKArgs, float*);
+template <int STAGE, bool TAPE>
+constexpr FwdKernel k_parts2 = k_query_fwd_parts<STAGE, 2, TAPE>;
+template <int STAGE, bool TAPE>
+constexpr FwdKernel k_parts3 = k_query_fwd_parts<STAGE, 3, TAPE>;
+}  // namespace
+// The <STAGE, TAPE> instantiation of a decoder-parallel forward kernel K for cfg: the fine stage, or the
+// colour stage with / without the activation tape (local to nslam_query_fwd_ws)
+#define COLOR_KERNEL(K) (cfg->act_tape ? K<NSLAM_STAGE_COLOR, true> : K<NSLAM_STAGE_COLOR, false>)
+#define STAGE_KERNEL(K) (cfg->stage == NSLAM_STAGE_FINE ? K<NSLAM_STAGE_FINE, false> : COLOR_KERNEL(K))
 
 extern "C" int nslam_query_fwd_ws(const nslam_query_cfg* cfg, const double* pts, int64_t n_pts, float* raw, void* ws,
                                   size_t ws_bytes, void* stream) {
@@ -39,20 +52,18 @@ extern "C" int nslam_query_fwd_ws(const nslam_query_cfg* cfg, const double* pts,
   const int rc = check_cfg(cfg, false);
   if (rc) return rc;
   if (!ws || ws_bytes < need) return NSLAM_EWORKSPACE;
-  if ((!pts && !cfg->rays_o) || !raw || (((uintptr_t)raw) & 15)) return NSLAM_EINVAL;
-  if (cfg->rays_o && (n_pts >= (int64_t(1) << 31) || n_pts % cfg->n_samples)) return NSLAM_EINVAL;
-  QueryKArgs a{*cfg, pts, n_pts, raw, nullptr, nullptr};
-  const int64_t groups = ((n_pts + 31) / 32 + 3) / 4;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  float* occ = reinterpret_cast<float*>(ws);
-  // Colour stage: 3 parts (middle | fine | colour) while 3 waves per tile fit the chip's wave slots
-  // in one round (3 per SIMD at the forward's 168 VGPRs; e.g. tracking, 300 tiles), else 2 parts
-  // (middle then colour | fine: fewer, balanced waves — room0 mapping: 3000 instead of 4500 for
-  // 4096 slots, 187 -> 198 M ray-samples/s).  NSLAM_FWD_PARTS=2|3 forces one (experiments).
-  static const int forced_parts = [] {
-    const char* e = getenv("NSLAM_FWD_PARTS");
-    return e ? atoi(e) : 0;
+  if (check_points(cfg, pts, n_pts, raw != nullptr) || (((uintptr_t)raw) & 15)) return NSLAM_EINVAL;
+  // forward variant: cfg->fwd_variant, else NSLAM_FWD_MODE=units (one-wave workgroups per decoder-tile;
+  // the default), pc (producer / consumer waves, one persistent workgroup per CU) or parts
+  // (an unrecognised NSLAM_FWD_MODE is an error, not a silent fallback: a typo must not change the kernel)
+  static const int env_variant = [] {
+    const char* e = getenv("NSLAM_FWD_MODE");
+    if (!e || !*e || !strcmp(e, "units")) return (int)NSLAM_FWD_UNITS;
+    return !strcmp(e, "pc") ? (int)NSLAM_FWD_PC : !strcmp(e, "parts") ? (int)NSLAM_FWD_PARTS : -1;
   }();
+  if (cfg->fwd_variant < 0 || cfg->fwd_variant > NSLAM_FWD_PARTS) return NSLAM_EINVAL;
+  const int variant = cfg->fwd_variant == NSLAM_FWD_DEFAULT ? env_variant : cfg->fwd_variant;
+  if (variant < 0) return NSLAM_EINVAL;
   static const int64_t n_cus = [] {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -60,74 +71,79 @@ extern "C" int nslam_query_fwd_ws(const nslam_query_cfg* cfg, const double* pts,
       cus = 256;
     return (int64_t)cus;
   }();
-  const int64_t wave_slots = n_cus * 4 * 3;
-  const int64_t tiles = (n_pts + 31) / 32;
-  const int color_parts = forced_parts == 2 || forced_parts == 3 ? forced_parts : (3 * tiles <= wave_slots ? 3 : 2);
-  const dim3 b256(256);
-  // forward variant: cfg->fwd_variant, else NSLAM_FWD_MODE=pc (producer / consumer waves, one persistent
-  // workgroup per CU), units (one-wave workgroups per decoder-tile), dyn (a counter; experiment), parts
-  // (an unrecognised NSLAM_FWD_MODE is an error, not a silent fallback: a typo must not change the kernel)
-  static const int env_mode = [] {
-    const char* e = getenv("NSLAM_FWD_MODE");
-    if (!e || !*e || !strcmp(e, "units")) return 1;
-    return !strcmp(e, "pc") ? 3 : !strcmp(e, "dyn") ? 2 : !strcmp(e, "parts") ? 0 : -1;
-  }();
-  if (cfg->fwd_variant < 0 || cfg->fwd_variant > NSLAM_FWD_PARTS) return NSLAM_EINVAL;
-  if (cfg->fwd_variant == NSLAM_FWD_DEFAULT && env_mode < 0) return NSLAM_EINVAL;
-  const int mode = cfg->fwd_variant == NSLAM_FWD_UNITS ? 1
-                   : cfg->fwd_variant == NSLAM_FWD_PC  ? 3
-                   : cfg->fwd_variant == NSLAM_FWD_PARTS ? 0
-                                                         : env_mode;
-  if (mode == 3) {
-    const int64_t units = tiles * (cfg->stage == NSLAM_STAGE_COLOR ? 3 : 2);
-    const dim3 g((unsigned)(units < n_cus ? units : n_cus)), b(64 * kPcWaves);
-    if (cfg->stage == NSLAM_STAGE_FINE)
-      hipLaunchKernelGGL((k_query_fwd_pc<NSLAM_STAGE_FINE, false>), g, b, 0, s, a, occ);
-    else if (cfg->act_tape)
-      hipLaunchKernelGGL((k_query_fwd_pc<NSLAM_STAGE_COLOR, true>), g, b, 0, s, a, occ);
-    else
-      hipLaunchKernelGGL((k_query_fwd_pc<NSLAM_STAGE_COLOR, false>), g, b, 0, s, a, occ);
-  } else if (mode == 1) {
-    const int np = cfg->stage == NSLAM_STAGE_COLOR ? 3 : 2;
-    const dim3 g((unsigned)(tiles * np)), b64(64);
-    if (cfg->stage == NSLAM_STAGE_FINE)
-      hipLaunchKernelGGL((k_query_fwd_units<NSLAM_STAGE_FINE, false>), g, b64, 0, s, a, occ);
-    else if (cfg->act_tape)
-      hipLaunchKernelGGL((k_query_fwd_units<NSLAM_STAGE_COLOR, true>), g, b64, 0, s, a, occ);
-    else
-      hipLaunchKernelGGL((k_query_fwd_units<NSLAM_STAGE_COLOR, false>), g, b64, 0, s, a, occ);
-  } else if (mode == 2) {
-    const int np = cfg->stage == NSLAM_STAGE_COLOR ? 3 : 2;
-    unsigned* ctr = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + (need - 256));
-    if (hipMemsetAsync(ctr, 0, 8, s) != hipSuccess) return hip_status();
-    const int64_t waves = tiles * np < wave_slots ? tiles * np : wave_slots;
-    const dim3 g((unsigned)((waves + 3) / 4));
-    if (cfg->stage == NSLAM_STAGE_FINE)
-      hipLaunchKernelGGL((k_query_fwd_dyn<NSLAM_STAGE_FINE, false>), g, b256, 0, s, a, occ, ctr);
-    else if (cfg->act_tape)
-      hipLaunchKernelGGL((k_query_fwd_dyn<NSLAM_STAGE_COLOR, true>), g, b256, 0, s, a, occ, ctr);
-    else
-      hipLaunchKernelGGL((k_query_fwd_dyn<NSLAM_STAGE_COLOR, false>), g, b256, 0, s, a, occ, ctr);
-  } else if (cfg->stage == NSLAM_STAGE_FINE)
-    hipLaunchKernelGGL((k_query_fwd_parts<NSLAM_STAGE_FINE, 2, false>), dim3((unsigned)(groups * 2)), b256, 0, s, a,
-                       occ);
-  else if (color_parts == 2 && cfg->act_tape)
-    hipLaunchKernelGGL((k_query_fwd_parts<NSLAM_STAGE_COLOR, 2, true>), dim3((unsigned)(groups * 2)), b256, 0, s, a,
-                       occ);
-  else if (color_parts == 2)
-    hipLaunchKernelGGL((k_query_fwd_parts<NSLAM_STAGE_COLOR, 2, false>), dim3((unsigned)(groups * 2)), b256, 0, s, a,
-                       occ);
-  else if (cfg->act_tape)
-    hipLaunchKernelGGL((k_query_fwd_parts<NSLAM_STAGE_COLOR, 3, true>), dim3((unsigned)(groups * 3)), b256, 0, s, a,
-                       occ);
-  else
-    hipLaunchKernelGGL((k_query_fwd_parts<NSLAM_STAGE_COLOR, 3, false>), dim3((unsigned)(groups * 3)), b256, 0, s, a,
-                       occ);
+  QueryKArgs a{*cfg, pts, n_pts, raw, nullptr, nullptr};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  float* occ = reinterpret_cast<float*>(ws);  // the middle occupancy [n_pts] (the 256 bytes after it: reserved)
+  const int64_t tiles = (n_pts + 31) / 32, groups = (tiles + 3) / 4;
+  const int64_t units = tiles * (cfg->stage == NSLAM_STAGE_COLOR ? 3 : 2);
+  if (variant == NSLAM_FWD_PC) {
+    hipLaunchKernelGGL(STAGE_KERNEL(k_query_fwd_pc), dim3((unsigned)(units < n_cus ? units : n_cus)),
+                       dim3(64 * kPcWaves), 0, s, a, occ);
+  } else if (variant == NSLAM_FWD_UNITS) {
+    hipLaunchKernelGGL(STAGE_KERNEL(k_query_fwd_units), dim3((unsigned)units), dim3(64), 0, s, a, occ);
+  } else if (cfg->stage == NSLAM_STAGE_COLOR && 3 * tiles <= n_cus * 4 * 3) {
+    // Colour stage: 3 parts (middle | fine | colour) while 3 waves per tile fit the chip's wave slots
+    // in one round (3 per SIMD at the forward's 168 VGPRs; e.g. tracking, 300 tiles), else 2 parts
+    // (middle then colour | fine: fewer, balanced waves — room0 mapping: 3000 instead of 4500 for
+    // 4096 slots, 187 -> 198 M ray-samples/s)
+    hipLaunchKernelGGL(COLOR_KERNEL(k_parts3), dim3((unsigned)(groups * 3)), dim3(256), 0, s, a, occ);
+  } else {
+    hipLaunchKernelGGL(STAGE_KERNEL(k_parts2), dim3((unsigned)(groups * 2)), dim3(256), 0, s, a, occ);
+  }
   if (!cfg->defer_occ)  // else the consumer adds ws on read (nslam_loss_cfg.occ_add)
     hipLaunchKernelGGL(k_occ_combine, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, s, raw, occ, n_pts);
   return hip_status();
 }
+#undef STAGE_KERNEL
+#undef COLOR_KERNEL
 
+// base[j] += sum_b slab[b][j].  A workgroup owns 64 parameters; lane (r, c) of a wave reads the
+// float4 c of slab r of every 64th slab group, so the 16 waves x 4 lane rows keep 64 slab streams
+// in flight per workgroup (~count/64 workgroups fill the chip; a wave load is 4 x 256-B
+// segments).  The 64 partials are combined in LDS in a fixed order: deterministic.
+// Defined here once for the library: the decoder launchers (nslam_query_dec.hip) and launch_color_wgrad
+// reach it through slab_reduce (nslam_query_host.h).
+namespace nslamq {
+constexpr int kReduceWaves = 16;
+__global__ __launch_bounds__(64 * kReduceWaves) void k_slab_reduce(const float* __restrict__ slab, int64_t nslab,
+                                                                   int acc_floats, int count,
+                                                                   float* __restrict__ base) {
+  __shared__ f32x4 part[kReduceWaves * 4][16];
+  const int lane = threadIdx.x & 63, wave = wave_id();
+  const int c = lane & 15, r = wave * 4 + (lane >> 4);  // r: slab stream 0..63
+  const int j = (blockIdx.x * 16 + c) * 4;
+  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
+  if (j < count) {
+    const float* p = slab + j;
+    int64_t b = r;
+    for (; b + 64 < nslab; b += 128) {
+      s0 += *reinterpret_cast<const f32x4*>(p + b * acc_floats);
+      s1 += *reinterpret_cast<const f32x4*>(p + (b + 64) * acc_floats);
+    }
+    if (b < nslab) s0 += *reinterpret_cast<const f32x4*>(p + b * acc_floats);
+  }
+  part[r][c] = s0 + s1;
+  __syncthreads();
+  if (threadIdx.x < 16 && j < count) {
+    f32x4 t = part[0][c];
+#pragma unroll 8
+    for (int k = 1; k < kReduceWaves * 4; ++k) t += part[k][c];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (j + e < count) base[j + e] += t[e];
+  }
+}
+
+int slab_reduce(const nslam_dec_grad& dg, float* slab, bool folded, int64_t nslab, int64_t blocks, int acc,
+                hipStream_t s) {
+  const int64_t n = folded ? blocks : nslab;
+  const int stride = folded ? acc * kWavesBwd : acc;
+  const int64_t nblk = (dg.count + 63) / 64;
+  hipLaunchKernelGGL(k_slab_reduce, dim3((unsigned)nblk), dim3(64 * kReduceWaves), 0, s, slab, n, stride,
+                     (int)dg.count, dg.base);
+  return hip_status();
+}
+}  // namespace nslamq
 
 extern "C" int nslam_query_bwd_decoder(const nslam_query_cfg* cfg, int32_t dec, int32_t accumulate_pts,
                                        const double* pts, int64_t n_pts, const float* g_raw, double* g_pts, void* ws,
@@ -135,8 +151,7 @@ extern "C" int nslam_query_bwd_decoder(const nslam_query_cfg* cfg, int32_t dec, 
   const int rc = check_cfg(cfg, true);
   if (rc) return rc;
   if (dec < 0 || dec > 3 || !stage_uses(cfg->stage, dec)) return NSLAM_EINVAL;
-  if (n_pts < 0 || (n_pts > 0 && ((!pts && !cfg->rays_o) || !g_raw))) return NSLAM_EINVAL;
-  if (cfg->rays_o && (n_pts >= (int64_t(1) << 31) || n_pts % cfg->n_samples)) return NSLAM_EINVAL;
+  if (check_points(cfg, pts, n_pts, g_raw != nullptr)) return NSLAM_EINVAL;
   if (cfg->need_pts_grad && n_pts > 0 && !g_pts) return NSLAM_EINVAL;
   if (n_pts == 0) return NSLAM_OK;
   if (cfg->dgrad[dec].base && cfg->dgrad[dec].count <= 0) return NSLAM_EUNSUPPORTED;
@@ -178,8 +193,7 @@ extern "C" int nslam_query_bwd(const nslam_query_cfg* cfg, const double* pts, in
                                double* g_pts, void* ws, size_t ws_bytes, void* stream) {
   const int rc = check_cfg(cfg, true);
   if (rc) return rc;
-  if (n_pts < 0 || (n_pts > 0 && ((!pts && !cfg->rays_o) || !g_raw))) return NSLAM_EINVAL;
-  if (cfg->rays_o && (n_pts >= (int64_t(1) << 31) || n_pts % cfg->n_samples)) return NSLAM_EINVAL;
+  if (check_points(cfg, pts, n_pts, g_raw != nullptr)) return NSLAM_EINVAL;
   if (cfg->need_pts_grad && n_pts > 0 && !g_pts) return NSLAM_EINVAL;
   if (n_pts == 0) return NSLAM_OK;
   for (int d = 0; d < 4; ++d)

@@ -4,7 +4,7 @@
 #ifndef NSLAM_DEC
 #error "build with -DNSLAM_DEC=0..3"
 #endif
-#include "nslam_query_impl.h"
+#include "nslam_query_bwd.h"
 
 namespace nslamq {
 template int dispatch_dec_bwd<NSLAM_DEC>(const QueryKArgs&, bool, float*, hipStream_t);

@@ -1,8 +1,8 @@
 // nslam_query_multi.hip — ABI v10 nslam_query_bwd_decoders (the mask-only backward of several decoders
-// in one launch, k_dec_bwd_multi in nslam_query_impl.h) and ABI v16 nslam_color_wgrad (the colour
+// in one launch, k_dec_bwd_multi in nslam_query_bwd.h) and ABI v16 nslam_color_wgrad (the colour
 // decoder's parameter gradients, k_color_wgrad in nslam_color_wgrad.hip).  Its own translation unit:
 // the multi-decoder kernel instantiates every decoder's backward tile.
-#include "nslam_query_impl.h"
+#include "nslam_query_bwd.h"
 
 using namespace nslamq;
 
@@ -11,8 +11,7 @@ extern "C" int nslam_query_bwd_decoders(const nslam_query_cfg* cfg, int32_t dec_
   const int rc = check_cfg(cfg, true);
   if (rc) return rc;
   if (dec_mask <= 0 || dec_mask > 15) return NSLAM_EINVAL;
-  if (n_pts < 0 || (n_pts > 0 && ((!pts && !cfg->rays_o) || !g_raw))) return NSLAM_EINVAL;
-  if (cfg->rays_o && (n_pts >= (int64_t(1) << 31) || n_pts % cfg->n_samples)) return NSLAM_EINVAL;
+  if (check_points(cfg, pts, n_pts, g_raw != nullptr)) return NSLAM_EINVAL;
   if (cfg->need_pts_grad && n_pts > 0 && !g_pts) return NSLAM_EINVAL;
   MultiDecArgs m{};
   for (int d = 0; d < 4; ++d) {
@@ -145,8 +144,7 @@ extern "C" int nslam_live_points(const nslam_query_cfg* cfg, int32_t dec_mask, c
   const int rc = check_cfg(cfg, true);
   if (rc) return rc;
   if (dec_mask <= 0 || dec_mask > 15 || !live_idx || !n_live) return NSLAM_EINVAL;
-  if (n_pts < 0 || n_pts >= (int64_t(1) << 31) || (n_pts > 0 && !pts && !cfg->rays_o)) return NSLAM_EINVAL;
-  if (cfg->rays_o && n_pts % cfg->n_samples) return NSLAM_EINVAL;
+  if (check_points(cfg, pts, n_pts, true, /*index32=*/true)) return NSLAM_EINVAL;  // (the lists are int32)
   LiveArgs m{};
   for (int d = 0; d < 4; ++d) {
     if (!((dec_mask >> d) & 1)) continue;
@@ -184,8 +182,7 @@ extern "C" int nslam_query_bwd_decoders_live(const nslam_query_cfg* cfg, int32_t
   const int rc = check_cfg(cfg, true);
   if (rc) return rc;
   if (dec_mask <= 0 || dec_mask > 15 || !live_idx || !n_live) return NSLAM_EINVAL;
-  if (n_pts < 0 || (n_pts > 0 && ((!pts && !cfg->rays_o) || !g_raw))) return NSLAM_EINVAL;
-  if (n_pts >= (int64_t(1) << 31) || (cfg->rays_o && n_pts % cfg->n_samples)) return NSLAM_EINVAL;
+  if (check_points(cfg, pts, n_pts, g_raw != nullptr, /*index32=*/true)) return NSLAM_EINVAL;
   if (cfg->need_pts_grad) return NSLAM_EUNSUPPORTED;  // d/dpts is needed for every point
   MultiDecArgs m{};
   for (int d = 0; d < 4; ++d) {
@@ -219,8 +216,7 @@ extern "C" int nslam_color_wgrad(const nslam_query_cfg* cfg, const double* pts, 
   if (cfg->stage != NSLAM_STAGE_COLOR || n_pts < 0) return NSLAM_EINVAL;
   if (!cfg->dgrad[NSLAM_DEC_COLOR].base || cfg->dgrad[NSLAM_DEC_COLOR].count <= 0) return NSLAM_EUNSUPPORTED;
   if (n_pts > 0 && !cw_tape_path(cfg)) return NSLAM_EUNSUPPORTED;
-  if (n_pts > 0 && ((!pts && !cfg->rays_o) || !g_raw)) return NSLAM_EINVAL;
-  if (cfg->rays_o && (n_pts >= (int64_t(1) << 31) || n_pts % cfg->n_samples)) return NSLAM_EINVAL;
+  if (check_points(cfg, pts, n_pts, g_raw != nullptr)) return NSLAM_EINVAL;
   if (n_pts == 0) return NSLAM_OK;
   if (!ws || ws_bytes < dec_ws_bytes(cfg, NSLAM_DEC_COLOR, n_pts)) return NSLAM_EWORKSPACE;
   QueryKArgs a{*cfg, pts, n_pts, nullptr, g_raw, nullptr};

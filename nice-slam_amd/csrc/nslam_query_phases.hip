@@ -2,6 +2,7 @@
 // s_memtime buffer g_phase must be a single device symbol that nslam_debug_phases can read).
 #define NSLAM_QUERY_ONE_TU
 #include "nslam_query.hip"
+#include "nslam_query_bwd.h"
 
 namespace nslamq {
 template int dispatch_dec_bwd<NSLAM_DEC_COARSE>(const QueryKArgs&, bool, float*, hipStream_t);

@@ -333,3 +333,130 @@ def test_v21_gather_frame_needs_a_pose_or_a_camera(pkg):
     args = [fr, 1, 10, 4096, 96, 128, 0, 96, 0, 128, 500.0, 500.0, 64.0, 48.0, None, None, 4096, 4096, 4096, 4096,
             None, None, None, None]
     assert L.nslam_gather_rays(*args) == -1
+
+
+_POINT_EPS = ("fwd", "fwd_ws", "bwd", "bwd_decoder", "bwd_decoders", "bwd_decoders_live", "live_points",
+              "color_wgrad")
+
+
+def _point_call(pkg, ep, pts, n, buf, rays=0, **cfg_fields):
+    """One of the eight point-taking entry points on a colour-stage config whose other arguments are all
+    acceptable (fake aligned pointers): pts, n and buf (the output row buffer of the forwards, the cotangent
+    g_raw of the backwards; nslam_live_points has neither) decide the return code.  rays > 0: the ray form
+    with that many samples per ray."""
+    lib, L = pkg._lib, pkg._lib.lib()
+    cfg = _colour_cfg(pkg)
+    cfg.saved_masks = 4096
+    if ep == "color_wgrad":
+        cfg.act_tape = 4096
+        cfg.dgrad[lib.DEC_COLOR].base = 4096
+        cfg.dgrad[lib.DEC_COLOR].count = 15575
+    if rays:
+        cfg.rays_o = cfg.rays_d = cfg.z_vals = 4096
+        cfg.n_samples = rays
+    for k, v in cfg_fields.items():
+        if k == "dgrad_base":
+            cfg.dgrad[lib.DEC_COLOR].base = v
+        else:
+            setattr(cfg, k, v)
+    c = ctypes.byref(cfg)
+    four = (ctypes.c_void_p * 4)(4096, 4096, 4096, 4096)
+    colour, big = 1 << lib.DEC_COLOR, 1 << 62
+    if ep == "fwd":
+        return L.nslam_query_fwd(c, pts, n, buf, None)
+    if ep == "fwd_ws":
+        return L.nslam_query_fwd_ws(c, pts, n, buf, 4096, L.nslam_query_fwd_workspace_size(c, n), None)
+    if ep == "bwd":
+        return L.nslam_query_bwd(c, pts, n, buf, 4096, 4096, big, None)
+    if ep == "bwd_decoder":
+        return L.nslam_query_bwd_decoder(c, lib.DEC_COLOR, 0, pts, n, buf, 4096, 4096, big, None)
+    if ep == "bwd_decoders":
+        return L.nslam_query_bwd_decoders(c, colour, pts, n, buf, four, None)
+    if ep == "bwd_decoders_live":
+        return L.nslam_query_bwd_decoders_live(c, colour, pts, n, buf, four, four, None)
+    if ep == "live_points":
+        return L.nslam_live_points(c, colour, pts, n, four, four, 4096, big, None)
+    assert ep == "color_wgrad"
+    return L.nslam_color_wgrad(c, pts, n, buf, 4096, big, None)
+
+
+# (case, pts, n_pts, buf, samples per ray, config fields): what is wrong with the points of the call
+_POINT_CASES = [
+    ("negative count", 4096, -1, 4096, 0, {}),
+    ("no points", None, 64, 4096, 0, {}),
+    ("rays: ragged count", None, 100, 4096, 48, {}),
+    ("rays: 2^31 points", None, 1 << 31, 4096, 32, {}),
+    ("rays: 2^31 points, ragged", None, (1 << 31) + 1, 4096, 32, {}),
+    ("no row buffer", 4096, 64, None, 0, {}),
+    # doubly wrong calls: the order of the checks decides the code
+    ("negative count, no decoder gradient", 4096, -1, 4096, 0, {"dgrad_base": None}),
+    ("no points, no saved masks", None, 64, 4096, 0, {"saved_masks": None}),
+    ("no points, parameter gradients asked", None, 64, 4096, 0, {"dgrad_base": 4096}),
+    ("no points, d/dpts asked", None, 64, 4096, 0, {"need_pts_grad": 1}),
+    ("rays: ragged count, d/dpts asked", None, 100, 4096, 48, {"need_pts_grad": 1}),
+    ("no row buffer, parameter gradients asked", 4096, 64, None, 0, {"dgrad_base": 4096}),
+    ("no row buffer, no saved masks", 4096, 64, None, 0, {"saved_masks": None}),
+]
+# pts form: only the live-point entry points index points in 32 bits whatever the form
+_LIVE_CASES = [("pts: 2^31 points", 4096, 1 << 31, 4096, 0, {})]
+
+# return codes of the parent commit's library (recorded from its build, before check_points existed), in
+# _POINT_EPS order; None: the entry point has no such argument
+_POINT_RC = {
+    "negative count": (-1, -1, -1, -1, -1, -1, -1, -1),
+    "no points": (-1, -1, -1, -1, -1, -1, -1, -1),
+    "rays: ragged count": (-1, -1, -1, -1, -1, -1, -1, -1),
+    "rays: 2^31 points": (-1, -1, -1, -1, -1, -1, -1, -1),
+    "rays: 2^31 points, ragged": (-1, -1, -1, -1, -1, -1, -1, -1),
+    "no row buffer": (-1, -1, -1, -1, -1, -1, None, -1),
+    "negative count, no decoder gradient": (-1, -1, -1, -1, -1, -1, -1, -1),
+    "no points, no saved masks": (-1, -1, -1, -1, -1, -1, -1, -2),
+    "no points, parameter gradients asked": (-1, -1, -1, -1, -1, -1, -1, -1),
+    "no points, d/dpts asked": (-1, -1, -1, -1, -1, -1, -1, -1),
+    "rays: ragged count, d/dpts asked": (-1, -1, -1, -1, -1, -1, -1, -1),
+    "no row buffer, parameter gradients asked": (-1, -1, -1, -1, -1, -1, None, -1),
+    "no row buffer, no saved masks": (-1, -1, -1, -1, -1, -1, None, -2),
+    "pts: 2^31 points": (-1, -1),
+}
+
+
+def test_point_argument_return_codes(pkg):
+    """The point-argument checks of the eight point-taking entry points (one check_points helper): every
+    entry point returns the code it returned before the checks were merged, for every bad-argument case
+    — each before any HIP call."""
+    for case, pts, n, buf, rays, fields in _POINT_CASES + _LIVE_CASES:
+        want = _POINT_RC[case]
+        eps = _POINT_EPS if (case, pts, n, buf, rays, fields) in _POINT_CASES else ("bwd_decoders_live", "live_points")
+        assert len(want) == len(eps)
+        for ep, rc in zip(eps, want):
+            if rc is None:
+                continue
+            assert rc in (-1, -2, -3), (case, ep)  # an argument error, never a launch
+            assert _point_call(pkg, ep, pts, n, buf, rays, **fields) == rc, (case, ep)
+
+
+_FWD_MODE_CHILD = """
+import ctypes, sys
+L = ctypes.CDLL(sys.argv[1])
+cfg = ctypes.create_string_buffer(bytes.fromhex(sys.argv[2]))
+vp, i64, sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_size_t
+L.nslam_query_fwd_workspace_size.argtypes, L.nslam_query_fwd_workspace_size.restype = [vp, i64], sz
+L.nslam_query_fwd_ws.argtypes = [vp, vp, i64, vp, vp, sz, vp]
+need = L.nslam_query_fwd_workspace_size(cfg, 64)
+print(need, L.nslam_query_fwd_ws(cfg, 4096, 64, 4096, 4096, need, None))
+"""
+
+
+def test_fwd_mode_rejects_retired_and_unknown_values(pkg):
+    """NSLAM_FWD_MODE accepts units, pc and parts: the retired dyn and a misspelt value are NSLAM_EINVAL
+    before any launch (the variable is read once per process, hence the child processes), and the forward
+    workspace keeps its size (the retired variant's 256 reserved bytes included)."""
+    import sys
+    cfg = _colour_cfg(pkg)
+    assert pkg._lib.lib().nslam_query_fwd_workspace_size(ctypes.byref(cfg), 64) == 256 + 256
+    argv = [sys.executable, "-c", _FWD_MODE_CHILD, pkg._lib.LIB_PATH, bytes(cfg).hex()]
+    kids = [subprocess.Popen(argv, env=dict(os.environ, NSLAM_FWD_MODE=mode), stdout=subprocess.PIPE, text=True)
+            for mode in ("dyn", "unit")]
+    for kid in kids:
+        out = kid.communicate()[0].split()
+        assert kid.returncode == 0 and out == ["512", "-1"], out
