@@ -383,7 +383,9 @@ int nslam_cam_grad(const float* cam, const float* c2w, const double* g_pts, cons
  * nslam_query_bwd_decoders — summed per point in buffer order ((g0 + g1) + g2, float64), over up to
  * 32 workgroups whose partial sums meet in ws (NSLAM_CAM_GRAD_WS_DOUBLES doubles; the last workgroup,
  * by `ticket` — a device uint32 zeroed once and re-armed by the call — adds them in workgroup order:
- * deterministic).  Replaces the buffer adds + single-workgroup nslam_cam_grad of a tracking iteration. */
+ * deterministic).  Replaces the buffer adds + single-workgroup nslam_cam_grad of a tracking iteration.
+ * nslam_cam_grad is one workgroup of the same kernel over one buffer (no ws, no ticket): up to 1024 points,
+ * where this call is one workgroup too, the two give the same bits. */
 #define NSLAM_CAM_GRAD_WS_DOUBLES (32 * 12)
 int nslam_cam_grad_parts(const float* cam, const float* c2w, const double* const* g_pts, int32_t n_parts,
                          const double* z_vals, const float* rays_d, int64_t n_rays, int32_t n_samples, float* g_cam,
@@ -443,15 +445,14 @@ int nslam_frustum_rows(const double* uvz, const uint8_t* near, const float* dept
                        void* ws, size_t ws_bytes, void* stream);
 size_t nslam_frustum_rows_workspace_size(int64_t n_vox);
 
-/* ABI v20.  The tracker's best-pose bookkeeping of one camera iteration (Tracker.py:245-247: if loss <
- * best_loss: best_loss = loss, candidate = camera_tensor), on the device: if *loss < *best_loss (float64),
- * *best_loss = *loss and best[0..n) = cam[0..n) (n <= 64, float32).  One single-wave launch. */
-int nslam_track_best(const double* loss, double* best_loss, const float* cam, float* best, int32_t n, void* stream);
 /* ABI v21.  The camera iteration's loss and its best-pose bookkeeping in one launch: *loss_out = the sum of
  * ray_loss[0..n_rays) (float64; a fixed-order tree over one workgroup: the same value every call), then,
- * when best_loss is not NULL, nslam_track_best's update with that sum (cam, best: n <= 64 float32).
- * Replaces optimize_cam_in_batch's loss.sum() (Tracker.py:110-123) and the comparison of Tracker.py:245-247,
- * so the tracker's camera loop needs no reduction launch of its own. */
+ * when best_loss is not NULL, the tracker's best-pose update with that sum (Tracker.py:245-247: if loss <
+ * best_loss: best_loss = loss, candidate = camera_tensor), on the device: if *loss_out < *best_loss
+ * (float64), *best_loss = *loss_out and best[0..n) = cam[0..n) (n <= 64, float32).
+ * Replaces optimize_cam_in_batch's loss.sum() (Tracker.py:110-123) and that comparison, so the tracker's
+ * camera loop needs no reduction launch and no host read-back.  (ABI v24 removed v20's nslam_track_best,
+ * the same update as a launch of its own, which this entry point and nslam_cam_grad_step superseded.) */
 int nslam_loss_sum_best(const double* ray_loss, int64_t n_rays, double* loss_out, double* best_loss, const float* cam,
                         float* best, int32_t n, void* stream);
 

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NSLAM_LIB") or os.path.join(_HERE, "libnslam.so")  # NSLAM_LIB: instrumented builds
 
 NSLAM_OK = 0
-ABI_VERSION = 23
+ABI_VERSION = 24
 STAGES = {"coarse": 0, "middle": 1, "fine": 2, "color": 3}
 DEC_COARSE, DEC_MIDDLE, DEC_FINE, DEC_COLOR = 0, 1, 2, 3
 
@@ -127,7 +127,7 @@ EXPORTS = (
     "nslam_render_loss_workspace_size", "nslam_adam_step", "nslam_rows_pack", "nslam_rows_unpack",
     "nslam_query_fwd_ws", "nslam_query_fwd_workspace_size", "nslam_cam_grad", "nslam_cam_pose",
     "nslam_query_tape_size", "nslam_color_wgrad", "nslam_cam_grad_parts", "nslam_cam_grad_batch",
-    "nslam_cam_pose_batch", "nslam_frustum_rows", "nslam_frustum_rows_workspace_size", "nslam_track_best",
+    "nslam_cam_pose_batch", "nslam_frustum_rows", "nslam_frustum_rows_workspace_size",
     "nslam_loss_sum_best", "nslam_cam_vector_batch", "nslam_cam_grad_step",
     # mesh extraction (additive: no ABI bump)
     "nslam_point_masks", "nslam_point_masks_workspace_size", "nslam_mc_count", "nslam_mc_emit",
@@ -202,7 +202,6 @@ def lib():
         L.nslam_frustum_rows.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
         L.nslam_frustum_rows_workspace_size.argtypes = [i64]
         L.nslam_frustum_rows_workspace_size.restype = sz
-        L.nslam_track_best.argtypes = [vp, vp, vp, vp, i32, vp]
         L.nslam_loss_sum_best.argtypes = [vp, i64, vp, vp, vp, vp, i32, vp]
         L.nslam_cam_vector_batch.argtypes = [vp, i64, i32, vp, vp, vp]
         L.nslam_cam_grad_step.argtypes = [ctypes.POINTER(NslamCamTail), vp, ctypes.POINTER(vp), i32, vp, vp, i64, i32,

@@ -401,11 +401,6 @@ __global__ __launch_bounds__(256) void k_render_loss(LossArgs a) {
   if (a.g_raw) ray_bwd(sm, nch, S, o.d, gd, 0.0, gc0, gc1, gc2, a.g_raw + ray * (int64_t)S * 4, lane);
 }
 
-int hip_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NSLAM_OK : NSLAM_EHIP - (int)e;
-}
-
 }  // namespace
 
 extern "C" int nslam_composite_fwd(const float* raw, const double* z_vals, int64_t n_rays, int32_t n_samples,

@@ -22,6 +22,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
+// the status every entry point returns after its launches (host)
+inline int hip_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? NSLAM_OK : NSLAM_EHIP - (int)e;
+}
+
 #define NSLAM_FRAG 1024  // floats per packed fragment block (16 steps x 64 lanes)
 #define TPITCH 33        // LDS row pitch of a transposed tile [32 points][33]
 #define TILE_FLOATS (32 * TPITCH)
@@ -474,6 +480,21 @@ __device__ __forceinline__ float fcos(float x) {
   const float s = sin_poly(r), c = cos_poly(r);
   const float v = (q & 1) ? s : c;
   return ((q + 1) & 2) ? -v : v;
+}
+
+// get_camera_from_tensor (common.py:137-176): c2w [3][4] from the 7-vector (quad2rotation's products and
+// differences, no FMA contraction); the one arithmetic of k_cam_pose, k_cam_pose_batch (nslam_camera.hip)
+// and the gather (nslam_mapping.hip)
+__device__ __forceinline__ void cam_pose_one(const float* __restrict__ cam, float* __restrict__ c2w) {
+  const float qr = cam[0], qi = cam[1], qj = cam[2], qk = cam[3];
+  const float two_s = 2.0f / (((qr * qr + qi * qi) + qj * qj) + qk * qk);
+  const float R[9] = {1.0f - two_s * (qj * qj + qk * qk), two_s * (qi * qj - qk * qr), two_s * (qi * qk + qj * qr),
+                      two_s * (qi * qj + qk * qr), 1.0f - two_s * (qi * qi + qk * qk), two_s * (qj * qk - qi * qr),
+                      two_s * (qi * qk - qj * qr), two_s * (qj * qk + qi * qr), 1.0f - two_s * (qi * qi + qj * qj)};
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) c2w[4 * i + j] = R[3 * i + j];
+    c2w[4 * i + 3] = cam[4 + i];
+  }
 }
 
 // ------------------------------------------------------------------------------------------

@@ -200,6 +200,5 @@ extern "C" int nslam_frustum_rows(const double* uvz, const uint8_t* near, const 
   hipLaunchKernelGGL(k_frustum_mask, g, b, 0, s, a);
   hipLaunchKernelGGL(k_frustum_scan, dim3(1), dim3(1024), 0, s, a.counts, nb, n_live);
   hipLaunchKernelGGL(k_frustum_compact, g, b, 0, s, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NSLAM_OK : NSLAM_EHIP - (int)e;
+  return hip_status();
 }

@@ -77,11 +77,6 @@ __global__ __launch_bounds__(256) void k_grid_bwd(const float* __restrict__ grid
   }
 }
 
-int hip_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NSLAM_OK : NSLAM_EHIP - (int)e;
-}
-
 }  // namespace
 
 extern "C" int nslam_grid_sample_fwd(const float* grid, const int32_t* dims, const float* coords, int64_t n,

@@ -18,10 +18,6 @@ namespace {
 constexpr int kMeshThreads = 256;
 
 inline int64_t blocks_for(int64_t n) { return (n + kMeshThreads - 1) / kMeshThreads; }
-inline int launch_rc() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NSLAM_OK : NSLAM_EHIP - (int)e;
-}
 
 // ------------------------------------------------------------------------------------------------
 // point masks
@@ -409,7 +405,7 @@ extern "C" int nslam_point_masks(const float* pts, int64_t n, const float* w2c, 
     }
   }
   hipLaunchKernelGGL(k_mask_points, g, b, 0, s, a);
-  return launch_rc();
+  return hip_status();
 }
 
 extern "C" size_t nslam_mc_workspace_size(int32_t nx, int32_t ny, int32_t nz) {
@@ -439,7 +435,7 @@ extern "C" int nslam_mc_count(const float* vol, int32_t nx, int32_t ny, int32_t 
   a.ntri = a.flags + 3 * n;
   hipLaunchKernelGGL(k_mc_count, dim3((unsigned)blocks_for(n)), dim3(kMeshThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
-  return launch_rc();
+  return hip_status();
 }
 
 extern "C" int nslam_mc_emit(const float* vol, int32_t nx, int32_t ny, int32_t nz, float level, const double* origin,
@@ -462,7 +458,7 @@ extern "C" int nslam_mc_emit(const float* vol, int32_t nx, int32_t ny, int32_t n
   const int64_t n = (int64_t)nx * ny * nz;
   hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)blocks_for(n)), dim3(kMeshThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
-  return launch_rc();
+  return hip_status();
 }
 
 extern "C" int nslam_points_in_hull(const void* pts, int32_t is_double, int64_t n, const double* planes, int32_t m,
@@ -477,7 +473,7 @@ extern "C" int nslam_points_in_hull(const void* pts, int32_t is_double, int64_t 
     hipLaunchKernelGGL(k_in_hull<double>, g, b, 0, s, static_cast<const double*>(pts), n, planes, m, inside);
   else
     hipLaunchKernelGGL(k_in_hull<float>, g, b, 0, s, static_cast<const float*>(pts), n, planes, m, inside);
-  return launch_rc();
+  return hip_status();
 }
 
 extern "C" int nslam_mesh_face_cull(const int32_t* faces, int64_t n_faces, const uint8_t* vmask, int64_t n_verts,
@@ -487,7 +483,7 @@ extern "C" int nslam_mesh_face_cull(const int32_t* faces, int64_t n_faces, const
   if (!faces || !vmask || !keep || n_verts == 0) return NSLAM_EINVAL;
   hipLaunchKernelGGL(k_face_cull, dim3((unsigned)blocks_for(n_faces)), dim3(kMeshThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), faces, n_faces, vmask, keep);
-  return launch_rc();
+  return hip_status();
 }
 
 extern "C" int nslam_mesh_components(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
@@ -498,7 +494,7 @@ extern "C" int nslam_mesh_components(const double* verts, int64_t n_verts, const
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 gv((unsigned)blocks_for(n_verts)), gf((unsigned)blocks_for(n_faces)), b(kMeshThreads);
   hipLaunchKernelGGL(k_label_init, gv, b, 0, s, label, n_verts, area);
-  if (n_faces == 0) return launch_rc();
+  if (n_faces == 0) return hip_status();
   for (int64_t it = 0; it <= n_verts; ++it) {  // every round that changes something lowers a label
     if (hipMemsetAsync(flag, 0, 4, s) != hipSuccess) return NSLAM_EHIP - (int)hipGetLastError();
     hipLaunchKernelGGL(k_label_hook, gf, b, 0, s, faces, n_faces, label, flag);
@@ -510,7 +506,7 @@ extern "C" int nslam_mesh_components(const double* verts, int64_t n_verts, const
     if (!h) break;
   }
   hipLaunchKernelGGL(k_face_area, gf, b, 0, s, verts, faces, n_faces, label, area);
-  return launch_rc();
+  return hip_status();
 }
 
 extern "C" int nslam_mesh_select(const int32_t* faces, int64_t n_faces, const int32_t* label, const double* area,
@@ -522,7 +518,7 @@ extern "C" int nslam_mesh_select(const int32_t* faces, int64_t n_faces, const in
   hipLaunchKernelGGL(k_face_select, dim3((unsigned)blocks_for(n_faces)), dim3(kMeshThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), faces, n_faces, label, area, largest, threshold, keep,
                      used);
-  return launch_rc();
+  return hip_status();
 }
 
 extern "C" int nslam_mesh_remap(const int32_t* faces, int64_t n_faces, const int32_t* new_id, int32_t* out,
@@ -532,5 +528,5 @@ extern "C" int nslam_mesh_remap(const int32_t* faces, int64_t n_faces, const int
   if (!faces || !new_id || !out) return NSLAM_EINVAL;
   hipLaunchKernelGGL(k_face_remap, dim3((unsigned)blocks_for(3 * n_faces)), dim3(kMeshThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), faces, 3 * n_faces, new_id, out);
-  return launch_rc();
+  return hip_status();
 }

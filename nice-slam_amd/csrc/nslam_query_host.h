@@ -53,11 +53,6 @@ inline int check_points(const nslam_query_cfg* cfg, const double* pts, int64_t n
   return NSLAM_OK;
 }
 
-inline int hip_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NSLAM_OK : NSLAM_EHIP - (int)e;
-}
-
 inline bool stage_uses(int stage, int dec) {
   switch (stage) {
     case NSLAM_STAGE_COARSE: return dec == NSLAM_DEC_COARSE;

@@ -190,11 +190,6 @@ __global__ __launch_bounds__(256) void k_sample_wave(SamplerArgs a) {
   if (lane < S) out[rank] = v;
 }
 
-int hip_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? NSLAM_OK : NSLAM_EHIP - (int)e;
-}
-
 }  // namespace
 
 extern "C" size_t nslam_workspace_size(int which, int64_t n) {
@@ -263,4 +258,5 @@ extern "C" const char* nslam_strerror(int code) {
 }
 
 // v9: nslam_cam_grad / nslam_cam_pose exports (they first shipped under v8 without a bump)
-extern "C" int nslam_abi_version(void) { return 23; }
+// v24: nslam_track_best removed (superseded by nslam_loss_sum_best, v21, and nslam_cam_grad_step, v23)
+extern "C" int nslam_abi_version(void) { return 24; }

@@ -750,15 +750,16 @@ class TrackingEngine:
         self.window = (he, self.H - he, we, self.W - we)
         self.w_color, self.handle_dynamic, self.use_color = w_color, handle_dynamic, use_color
         self.device = torch.device(device)
-        self._c2w = None
+        # the iteration's persistent buffers, made on its first call: the pose, the camera gradient's workspace
+        # and ticket (nslam_cam_grad_parts) and the last iteration's loss (device f64 scalar, overwritten by
+        # the next one)
+        self._c2w = self._cam_ws = self._cam_ticket = self._loss = None
         # ABI v15 nslam_cam_grad_parts: the frozen decoders' d/dpts buffers summed inside a
         # multi-workgroup camera-gradient kernel (no torch adds, no single-workgroup reduction)
         self.cam_parts = True
         # ABI v23 nslam_cam_grad_step: with a FusedAdam over the camera alone, its step, the loss sum and the
         # best pose run in the camera-gradient launch's last workgroup (two launches fewer per iteration)
         self.cam_tail = True
-        self._cam_ws = self._cam_ticket = None
-        self._loss = None  # the last iteration's loss (device f64 scalar, overwritten by the next one)
 
     def n_window(self):
         h0, h1, w0, w1 = self.window
@@ -786,6 +787,9 @@ class TrackingEngine:
         draw = self.eng.draws(seed) if pix is None else None
         if self._c2w is None:
             self._c2w = torch.empty(3, 4, dtype=torch.float32, device=cam.device)
+            self._cam_ws = torch.zeros(ops.CAM_GRAD_WS_DOUBLES, dtype=torch.float64, device=cam.device)
+            self._cam_ticket = torch.zeros(1, dtype=torch.int32, device=cam.device)
+            self._loss = torch.empty((), dtype=torch.float64, device=cam.device)
         # get_camera_from_tensor inside the gather (ABI v21), which also leaves the pose in self._c2w for
         # the camera gradient
         c2w = self._c2w
@@ -800,14 +804,7 @@ class TrackingEngine:
         if cam.grad is None:
             cam.grad = torch.empty_like(cam)
         if self.cam_parts:  # the decoders' d/dpts shares summed inside the multi-workgroup cam_grad (ABI v15)
-            if self._cam_ws is None:
-                self._cam_ws = torch.zeros(384, dtype=torch.float64, device=cam.device)
-                self._cam_ticket = torch.zeros(1, dtype=torch.int32, device=cam.device)
             gps = self.eng.query_bwd("color", ro, rd, z, g_raw, (), (), pts_grad=True, pts_parts=True)
-            if torch.is_tensor(gps):
-                gps = [gps]
-            if self._loss is None:
-                self._loss = torch.empty((), dtype=torch.float64, device=cam.device)
             if self.cam_tail and self._tail_ok(optimizer, cam):
                 ex, ex2, stp = optimizer.state_of(cam)
                 adam = (ex, ex2, stp, optimizer.group_of(cam)["lr"], *optimizer.betas, optimizer.eps)
@@ -824,8 +821,6 @@ class TrackingEngine:
         # the loss of the pose before the step (its rays' losses) and, with `best`, the best-pose update in
         # one launch: the candidate is the 7-vector right after that step, as the reference keeps it
         # (optimize_cam_in_batch steps before Tracker.py:245-247 compares)
-        if self._loss is None:
-            self._loss = torch.empty((), dtype=torch.float64, device=cam.device)
         if best is None:
             ops.loss_sum_best(ray_loss, self._loss)
         else:

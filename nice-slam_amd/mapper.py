@@ -460,7 +460,7 @@ class Mapper(object):
             if key not in self._graphs:
                 setup()  # eager warm-up: first-time allocations (engine capacity buffers, Adam state, caches)
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                with ops.capture(g):
                     out = setup()
                 self._graphs[key] = (g, out)
             g, (counts, n_samp) = self._graphs[key]
@@ -588,7 +588,7 @@ class Mapper(object):
                     losses = torch.zeros(n, dtype=torch.float64, device=dev) if hist is not None else None
                     g = torch.cuda.CUDAGraph()
                     eng._pre = None
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    with ops.capture(g):
                         if first:
                             cams_init()
                         for i in range(n):

@@ -7,7 +7,9 @@
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import gc
 import math
 
 import torch
@@ -67,6 +69,23 @@ _NOSPAN = _NoSpan()
 
 def _span(name):
     return TIMER.span(name) if TIMER is not None else _NOSPAN
+
+
+@contextlib.contextmanager
+def capture(graph):
+    """torch.cuda.graph(graph) with the garbage collector out of the way.  torch no longer collects before
+    a capture, and an automatic collection inside one may free a dead cycle's device objects (an older
+    graph, tensors of its pool) from the capturing thread, which the runtime does not allow while a stream
+    captures: the process aborts.  So dead cycles are collected first and none is collected inside."""
+    gc.collect()
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 _DEC_FOR_STAGE = {
@@ -643,12 +662,21 @@ class PixelDraws:
                                      self.rank, ptr(self.gt_max), ptr(self.key))
 
 
+CAM_GRAD_WS_DOUBLES = 32 * 12  # NSLAM_CAM_GRAD_WS_DOUBLES
+
+
+def _expect(fn, specs, msg=None):
+    """Every (tensor, dtype, shape) of specs is a contiguous tensor of exactly that dtype and shape, else
+    ValueError (fn: the caller's name; msg: its own wording instead of the expected / got line)."""
+    for t, dt, shp in specs:
+        if t.dtype != dt or tuple(t.shape) != tuple(shp) or not t.is_contiguous():
+            raise ValueError(f"{fn}: " + (msg or f"expected contiguous {dt} {shp}, got {t.dtype} {tuple(t.shape)}"))
+
+
 def cam_pose(cam, out):
     """nslam_cam_pose (ABI v8): out [3,4] f32 = get_camera_from_tensor(cam [7]) in one launch."""
-    if cam.dtype != torch.float32 or tuple(cam.shape) != (7,) or not cam.is_contiguous():
-        raise ValueError("cam_pose: cam must be a contiguous float32 [7]")
-    if out.dtype != torch.float32 or tuple(out.shape) != (3, 4) or not out.is_contiguous():
-        raise ValueError("cam_pose: out must be a contiguous float32 [3, 4]")
+    _expect("cam_pose", [(cam, torch.float32, (7,))], "cam must be a contiguous float32 [7]")
+    _expect("cam_pose", [(out, torch.float32, (3, 4))], "out must be a contiguous float32 [3, 4]")
     check(lib().nslam_cam_pose(ptr(cam), ptr(out), stream_ptr(cam.device)), "nslam_cam_pose")
     return out
 
@@ -658,10 +686,8 @@ def cam_grad(cam, c2w, g_pts, z, rd, out):
     get_camera_from_tensor (Renderer.py:172-174, common.py:137-176), from g_pts [N*S,3] f64,
     z [N,S] f64, rays_d [N,3] f32 and the c2w [3,4] f32 the rays were built with."""
     n, S = z.shape
-    for t, dt, shp in ((cam, torch.float32, (7,)), (c2w, torch.float32, (3, 4)), (g_pts, torch.float64, (n * S, 3)),
-                       (z, torch.float64, (n, S)), (rd, torch.float32, (n, 3)), (out, torch.float32, (7,))):
-        if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
-            raise ValueError(f"cam_grad: expected contiguous {dt} {shp}, got {t.dtype} {tuple(t.shape)}")
+    _expect("cam_grad", [(cam, torch.float32, (7,)), (c2w, torch.float32, (3, 4)), (g_pts, torch.float64, (n * S, 3)),
+                         (z, torch.float64, (n, S)), (rd, torch.float32, (n, 3)), (out, torch.float32, (7,))])
     with _span("cam_grad"):
         rc = lib().nslam_cam_grad(ptr(cam), ptr(c2w), ptr(g_pts), ptr(z), ptr(rd), n, S, ptr(out), stream_ptr(cam.device))
     check(rc, "nslam_cam_grad")
@@ -673,11 +699,10 @@ def cam_grad_parts(cam, c2w, g_pts, z, rd, out, ws, ticket):
     [N*S,3] f64, summed per point in list order inside the kernel) over several workgroups; ws: f64
     [NSLAM_CAM_GRAD_WS_DOUBLES], ticket: int32 [1] zeroed once (both persistent, one per caller)."""
     n, S = z.shape
-    for t, dt, shp in ((cam, torch.float32, (7,)), (c2w, torch.float32, (3, 4)), (z, torch.float64, (n, S)),
-                       (rd, torch.float32, (n, 3)), (out, torch.float32, (7,)), (ws, torch.float64, (384,)),
-                       (ticket, torch.int32, (1,))) + tuple((g, torch.float64, (n * S, 3)) for g in g_pts):
-        if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
-            raise ValueError(f"cam_grad_parts: expected contiguous {dt} {shp}, got {t.dtype} {tuple(t.shape)}")
+    _expect("cam_grad_parts", [(cam, torch.float32, (7,)), (c2w, torch.float32, (3, 4)), (z, torch.float64, (n, S)),
+                               (rd, torch.float32, (n, 3)), (out, torch.float32, (7,)),
+                               (ws, torch.float64, (CAM_GRAD_WS_DOUBLES,)), (ticket, torch.int32, (1,))] +
+            [(g, torch.float64, (n * S, 3)) for g in g_pts])
     bufs = (ctypes.c_void_p * len(g_pts))(*[ptr(g) for g in g_pts])
     with _span("cam_grad"):
         rc = lib().nslam_cam_grad_parts(ptr(cam), ptr(c2w), bufs, len(g_pts), ptr(z), ptr(rd), n, S, ptr(out), ptr(ws),
@@ -693,16 +718,14 @@ def cam_grad_step(cam, c2w, g_pts, z, rd, g_cam, ws, ticket, adam, ray_loss, los
     FusedAdam.step + loss_sum_best, in one launch."""
     n, S = z.shape
     ex, ex2, stp, lr, b1, b2, eps = adam
-    checks = ((cam, torch.float32, (7,)), (c2w, torch.float32, (3, 4)), (z, torch.float64, (n, S)),
-              (rd, torch.float32, (n, 3)), (g_cam, torch.float32, (7,)), (ws, torch.float64, (384,)),
+    checks = [(cam, torch.float32, (7,)), (c2w, torch.float32, (3, 4)), (z, torch.float64, (n, S)),
+              (rd, torch.float32, (n, 3)), (g_cam, torch.float32, (7,)), (ws, torch.float64, (CAM_GRAD_WS_DOUBLES,)),
               (ticket, torch.int32, (1,)), (ex, torch.float32, (7,)), (ex2, torch.float32, (7,)),
               (stp, torch.float32, (1,)), (ray_loss, torch.float64, (ray_loss.numel(),)),
-              (loss_out, torch.float64, ()))
+              (loss_out, torch.float64, ())]
     if best_loss is not None:
-        checks += ((best_loss, torch.float64, ()), (best, torch.float32, (7,)))
-    for t, dt, shp in checks + tuple((g, torch.float64, (n * S, 3)) for g in g_pts):
-        if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
-            raise ValueError(f"cam_grad_step: expected contiguous {dt} {shp}, got {t.dtype} {tuple(t.shape)}")
+        checks += [(best_loss, torch.float64, ()), (best, torch.float32, (7,))]
+    _expect("cam_grad_step", checks + [(g, torch.float64, (n * S, 3)) for g in g_pts])
     tail = _lib.NslamCamTail(ptr(cam), ptr(ex), ptr(ex2), ptr(stp), float(lr), float(b1), float(b2), float(eps),
                              ptr(ray_loss), ray_loss.numel(), ptr(loss_out), ptr(best_loss), ptr(best))
     bufs = (ctypes.c_void_p * len(g_pts))(*[ptr(g) for g in g_pts])
@@ -713,9 +736,6 @@ def cam_grad_step(cam, c2w, g_pts, z, rd, g_cam, ws, ticket, adam, ray_loss, los
     return loss_out
 
 
-CAM_GRAD_WS_DOUBLES = 32 * 12  # NSLAM_CAM_GRAD_WS_DOUBLES
-
-
 def cam_vector_batch(c2w, out, copy=None):
     """nslam_cam_vector_batch (ABI v22): out[k] = get_tensor_from_camera(c2w[k]) for c2w [n, 3|4, 4] f32
     (common.camera_tensors' arithmetic, one launch); copy: optional second [n, 7] f32 receiving the same."""
@@ -723,9 +743,8 @@ def cam_vector_batch(c2w, out, copy=None):
     if c2w.dtype != torch.float32 or c2w.dim() != 3 or c2w.shape[1] not in (3, 4) or c2w.shape[2] != 4 \
             or not c2w.is_contiguous() or not 1 <= n <= 64:
         raise ValueError("cam_vector_batch: c2w must be a contiguous float32 [n, 3|4, 4], 1 <= n <= 64")
-    for t in (out,) if copy is None else (out, copy):
-        if t.dtype != torch.float32 or tuple(t.shape) != (n, 7) or not t.is_contiguous():
-            raise ValueError("cam_vector_batch: out / copy must be contiguous float32 [n, 7]")
+    _expect("cam_vector_batch", [(t, torch.float32, (n, 7)) for t in ((out,) if copy is None else (out, copy))],
+            "out / copy must be contiguous float32 [n, 7]")
     rc = lib().nslam_cam_vector_batch(ptr(c2w), c2w.shape[1] * 4, n, ptr(out), None if copy is None else ptr(copy),
                                       stream_ptr(c2w.device))
     check(rc, "nslam_cam_vector_batch")
@@ -736,8 +755,7 @@ def cam_pose_batch(cams, c2w):
     """nslam_cam_pose_batch (ABI v19): c2w[k, :3, :4] = get_camera_from_tensor(cams[k]) for cams [n, 7] f32
     and c2w [n, 3 or 4, 4] f32 (both contiguous), one launch."""
     n = cams.shape[0]
-    if cams.dtype != torch.float32 or cams.dim() != 2 or cams.shape[1] != 7 or not cams.is_contiguous():
-        raise ValueError("cam_pose_batch: cams must be a contiguous float32 [n, 7]")
+    _expect("cam_pose_batch", [(cams, torch.float32, (n, 7))], "cams must be a contiguous float32 [n, 7]")
     if (c2w.dtype != torch.float32 or c2w.dim() != 3 or c2w.shape[0] != n or c2w.shape[1] not in (3, 4)
             or c2w.shape[2] != 4 or not c2w.is_contiguous()):
         raise ValueError("cam_pose_batch: c2w must be a contiguous float32 [n, 3|4, 4]")
@@ -747,19 +765,10 @@ def cam_pose_batch(cams, c2w):
     return c2w
 
 
-def track_best(loss, best_loss, cam, best):
-    """nslam_track_best (ABI v20): if loss < best_loss (float64 device scalars): best_loss = loss, best = cam."""
-    if loss.dtype != torch.float64 or best_loss.dtype != torch.float64 or cam.dtype != torch.float32 \
-            or best.shape != cam.shape or not (cam.is_contiguous() and best.is_contiguous()):
-        raise ValueError("track_best: float64 scalars and two contiguous float32 vectors of one shape")
-    check(lib().nslam_track_best(ptr(loss), ptr(best_loss), ptr(cam), ptr(best), cam.numel(), stream_ptr(cam.device)),
-          "nslam_track_best")
-
-
 def loss_sum_best(ray_loss, out, best_loss=None, cam=None, best=None):
     """nslam_loss_sum_best (ABI v21): out (float64 device scalar) = ray_loss.sum() in a fixed order (one
     workgroup: the same value on every call); with best_loss: if out < best_loss, best_loss = out and
-    best = cam (nslam_track_best's update, Tracker.py:245-247).  Returns out."""
+    best = cam (the tracker's best-pose update, Tracker.py:245-247).  Returns out."""
     if ray_loss.dtype != torch.float64 or out.dtype != torch.float64 or not ray_loss.is_contiguous():
         raise ValueError("loss_sum_best: a contiguous float64 ray_loss and a float64 scalar out")
     if best_loss is not None and (best_loss.dtype != torch.float64 or cam.dtype != torch.float32
@@ -778,14 +787,12 @@ def cam_grad_batch(cams, c2w, ray_begin, n_per, g_pts, z, rd, out, ws, tickets):
     """nslam_cam_grad_batch (ABI v19): out [n, 7] = d loss / d cams [n, 7] of the bundle-adjustment cameras,
     camera k's rays being [ray_begin[k], ray_begin[k] + n_per) of the batch (z [N, S] f64, rd [N, 3] f32,
     g_pts: list of [N*S, 3] f64 d/dpts shares); c2w [n, 3|4, 4] the poses rendered with; ws f64
-    [n * 384], tickets int32 [n] zeroed once (persistent per caller)."""
+    [n * NSLAM_CAM_GRAD_WS_DOUBLES], tickets int32 [n] zeroed once (persistent per caller)."""
     n = cams.shape[0]
     N, S = z.shape
-    for t, dt, shp in ((cams, torch.float32, (n, 7)), (z, torch.float64, (N, S)), (rd, torch.float32, (N, 3)),
-                       (out, torch.float32, (n, 7)), (ws, torch.float64, (n * CAM_GRAD_WS_DOUBLES,)),
-                       (tickets, torch.int32, (n,))) + tuple((g, torch.float64, (N * S, 3)) for g in g_pts):
-        if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
-            raise ValueError(f"cam_grad_batch: expected contiguous {dt} {shp}, got {t.dtype} {tuple(t.shape)}")
+    _expect("cam_grad_batch", [(cams, torch.float32, (n, 7)), (z, torch.float64, (N, S)), (rd, torch.float32, (N, 3)),
+                               (out, torch.float32, (n, 7)), (ws, torch.float64, (n * CAM_GRAD_WS_DOUBLES,)),
+                               (tickets, torch.int32, (n,))] + [(g, torch.float64, (N * S, 3)) for g in g_pts])
     if c2w.dtype != torch.float32 or c2w.dim() != 3 or c2w.shape[0] != n or not c2w.is_contiguous():
         raise ValueError("cam_grad_batch: c2w must be a contiguous float32 [n, 3|4, 4]")
     rb = (ctypes.c_int64 * n)(*[int(r) for r in ray_begin])

@@ -253,7 +253,7 @@ class Tracker(object):
             frame(zero_lr=True)
             opt.param_groups[0]["lr"] = self.cam_lr
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            with ops.capture(g):
                 frame()
             self._graphs[key] = g
             ctr.copy_(ctr0)

@@ -26,7 +26,7 @@ def test_library_exports_every_header_symbol(pkg):
 
 def test_abi_version_and_strerror(pkg):
     L = pkg._lib.lib()
-    assert L.nslam_abi_version() == pkg._lib.ABI_VERSION == 23
+    assert L.nslam_abi_version() == pkg._lib.ABI_VERSION == 24
     assert L.nslam_strerror(0) == b"ok"
     assert b"invalid" in L.nslam_strerror(-1)
 
@@ -201,9 +201,10 @@ def test_v16_color_wgrad_validates_without_gpu(pkg):
 
 def test_v16_removed_entry_points(pkg):
     """ABI v16 dropped the options measured neutral or slower in round 3 (the fused colour Adam, the
-    part-wise forward of the pipelined loop): they are no longer exported."""
+    part-wise forward of the pipelined loop), and ABI v24 dropped nslam_track_best (superseded by
+    nslam_loss_sum_best and nslam_cam_grad_step, no caller left): they are no longer exported."""
     L = pkg._lib.lib()
-    for name in ("nslam_color_wgrad_adam", "nslam_query_fwd_parts"):
+    for name in ("nslam_color_wgrad_adam", "nslam_query_fwd_parts", "nslam_track_best"):
         assert not hasattr(L, name), name
 
 

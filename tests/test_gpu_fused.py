@@ -784,6 +784,28 @@ def test_cam_grad_kernel_matches_autograd():
         assert float((out.cpu() - ref).norm() / ref.norm()) < 1e-5, n
 
 
+@pytest.mark.parametrize("n,S", [(1, 1), (3, 5), (21, 48), (64, 16)])
+def test_cam_grad_equals_single_workgroup_parts(n, S):
+    """nslam_cam_grad == nslam_cam_grad_parts with one d/dpts buffer, bit for bit, wherever the parts
+    launch is one workgroup (up to 1024 points: the smallest case, a partial wave, 1008 and 1024 points):
+    both are the one k_cam_grad_parts kernel, the same thread loop, shuffle and fixed-order sum."""
+    g = torch.Generator().manual_seed(17)
+    q = torch.randn(4, generator=g)
+    cam = torch.cat([q / q.norm(), torch.randn(3, generator=g) * 0.3]).float().to(DEV)
+    c2w = P.ops.cam_pose(cam, torch.empty(3, 4, dtype=torch.float32, device=DEV))
+    gp = torch.randn(n * S, 3, generator=g, dtype=torch.float64).to(DEV)
+    z = (torch.rand(n, S, generator=g, dtype=torch.float64) * 3).to(DEV)
+    rd = torch.randn(n, 3, generator=g).to(DEV)
+    out = torch.full((7,), -7.0, device=DEV)
+    out2 = torch.full((7,), 7.0, device=DEV)
+    ws = torch.zeros(P.ops.CAM_GRAD_WS_DOUBLES, dtype=torch.float64, device=DEV)
+    ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
+    P.ops.cam_grad(cam, c2w, gp, z, rd, out)
+    P.ops.cam_grad_parts(cam, c2w, [gp], z, rd, out2, ws, ticket)
+    assert bool(torch.isfinite(out).all()) and float(out.abs().sum()) > 0
+    assert torch.equal(out, out2), (out - out2).abs().max()
+
+
 def test_cam_pose_kernel_matches_get_camera_from_tensor():
     """nslam_cam_pose (ABI v9) vs the torch restatement of get_camera_from_tensor on the device.
     Same products and differences; |q|² may be summed in a different order than torch's reduce,
