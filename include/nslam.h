@@ -526,6 +526,61 @@ int nslam_mesh_select(const int32_t* faces, int64_t n_faces, const int32_t* labe
 /* out[f][c] = new_id[faces[f][c]]. */
 int nslam_mesh_remap(const int32_t* faces, int64_t n_faces, const int32_t* new_id, int32_t* out, void* stream);
 
+/* Evaluation (src/tools/cull_mesh.py, src/tools/eval_recon.py; csrc/nslam_eval.hip); additive, no ABI bump.
+ * No entry point here uses atomics: every output is the same from run to run.
+ *
+ * seen[i] = 1 when vertex i (float64 [n][3], cast to float32 as the reference does) projects into the image
+ * of any of n_frames cameras (cull_mesh.py:47-71, eval_recon.py:62-88).  w2c: device float32 [n_frames][16],
+ * row-major, inverted by the caller on the host.  Per vertex and frame, in float32 without FMA contraction:
+ * cam = w2c . [p, 1] (four products summed left to right), cam.x negated, uv = K . cam, z = uv.z + 1e-5,
+ * uv /= z; seen when 0 <= -z and 0 < u < W and 0 < v < H (strict).  A seen vertex reads no further frame. */
+int nslam_frustum_seen(const double* verts, int64_t n, const float* w2c, int32_t n_frames, int32_t H, int32_t W,
+                       float fx, float fy, float cx, float cy, uint8_t* seen, void* stream);
+
+/* area[f] = half the float64 cross-product norm of face f (faces int32 [n_faces][3] into verts float64
+ * [n_verts][3]).  The caller forms cdf = cumsum(area) on the device. */
+int nslam_face_areas(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, double* area,
+                     void* stream);
+/* `count` area-weighted surface samples (replaces trimesh.sample.sample_surface): sample i takes three
+ * uniforms u_k = (mix64(seed ^ mix64(i * 0x9e3779b97f4a7c15 + k)) >> 11) * 2^-53 (splitmix64's finaliser, the
+ * stream of the pixel draws), its face is the first f with cdf[f] > u0 * cdf[n_faces - 1] (binary search: a
+ * zero-area face is never chosen), the barycentric pair is reflected (u1 + u2 > 1: 1 - u1, 1 - u2) and the
+ * point is (v0 + u1 (v1 - v0)) + u2 (v2 - v0) in float64.  points float64 [count][3], face_id int32 [count]
+ * (NaN and -1 when the total area is not positive and finite). */
+int nslam_sample_surface(const double* verts, int64_t n_verts, const int32_t* faces, const double* cdf,
+                         int64_t n_faces, int64_t count, uint64_t seed, double* points, int32_t* face_id,
+                         void* stream);
+
+/* Exact float64 nearest neighbours on a uniform cell grid (replaces scipy's cKDTree and open3d's
+ * correspondence search).  The grid is lo (host double [3]), the cell edge `cell` and dims (host int32 [3],
+ * each >= 1, at most 2^24 cells in all); a point's cell is clamp(floor((p - lo) / cell), 0, dims - 1) per axis
+ * and its key (cx * dims[1] + cy) * dims[2] + cz.
+ * Build: keys int32 [m] of the targets (float64 [m][3]).  The caller sorts the targets by key (stable, so a
+ * cell keeps ascending original indices), keeps the permutation as orig_idx int32 [m] and forms cell_start
+ * int32 [cells + 1], the first sorted target of every cell (searchsorted).
+ * Query: one thread per query (float64 [n][3]); the query's cell is clamped into the grid and the rings of
+ * cells at Chebyshev radius r = 0, 1, 2, ... are scanned until best <= r * cell (every target beyond ring r
+ * differs from the query by more than r * cell along some axis, also for a query outside the box), until
+ * r * cell >= max_dist, or until the rings cover the grid.  dist float64 [n], idx int32 [n] (the ORIGINAL
+ * target index; ties go to the lowest).  max_dist < 0 or +inf: unbounded; else a neighbour farther than
+ * max_dist gives +inf and -1.  NSLAM_EINVAL: m <= 0, a non-finite lo / cell / max_dist, dims < 1 or more than
+ * 2^24 cells, n_cell_start != cells + 1. */
+int nslam_nn_build(const double* targets, int64_t m, const double* lo, double cell, const int32_t* dims,
+                   int32_t* keys, void* stream);
+int nslam_nn_query(const double* queries, int64_t n, const double* sorted_targets, const int32_t* orig_idx,
+                   int64_t m, const int32_t* cell_start, int64_t n_cell_start, const double* lo, double cell,
+                   const int32_t* dims, double max_dist, double* dist, int32_t* idx, void* stream);
+
+/* Point-to-point ICP.  out[i] = R p_i + t with rigid = host double [12], the row-major [3][4] matrix (R | t). */
+int nslam_transform_points(const double* pts, int64_t n, const double* rigid, double* out, void* stream);
+/* The Kabsch sums over the pairs (a_i = src[i], b_i = targets[idx[i]]) with 0 <= idx[i] < m: per workgroup of
+ * 1024 points 17 float64 partials [count, Σa (3), Σb (3), Σ a bᵀ (9, row-major), Σ |a - b|²] into
+ * partials[wg][17]; n_partials must equal the partial-count function's value for n.  Wave reduction by
+ * __shfl_down, then one LDS step; the caller sums the partials in index order. */
+int nslam_kabsch_sums(const double* src, const int32_t* idx, int64_t n, const double* targets, int64_t m,
+                      double* partials, int64_t n_partials, void* stream);
+int64_t nslam_kabsch_partials(int64_t n);
+
 enum { NSLAM_WS_SAMPLER = 0 };
 size_t nslam_workspace_size(int which, int64_t n);
 

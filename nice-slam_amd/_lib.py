@@ -135,6 +135,9 @@ EXPORTS = (
     "nslam_mesh_select", "nslam_mesh_remap",
     # live-point lists of the mask-only mapping backward (additive: no ABI bump)
     "nslam_live_points", "nslam_live_points_workspace_size", "nslam_query_bwd_decoders_live",
+    # evaluation: frustum culling, surface samples, nearest neighbours, ICP sums (additive: no ABI bump)
+    "nslam_frustum_seen", "nslam_face_areas", "nslam_sample_surface", "nslam_nn_build", "nslam_nn_query",
+    "nslam_transform_points", "nslam_kabsch_sums", "nslam_kabsch_partials",
 )
 
 _lib = None
@@ -226,6 +229,16 @@ def lib():
         L.nslam_live_points_workspace_size.restype = sz
         L.nslam_query_bwd_decoders_live.argtypes = [ctypes.POINTER(NslamQueryCfg), i32, vp, i64, vp,
                                                     ctypes.POINTER(vp), ctypes.POINTER(vp), vp]
+        u64, i32p = ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32)
+        L.nslam_frustum_seen.argtypes = [vp, i64, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp]
+        L.nslam_face_areas.argtypes = [vp, i64, vp, i64, vp, vp]
+        L.nslam_sample_surface.argtypes = [vp, i64, vp, vp, i64, i64, u64, vp, vp, vp]
+        L.nslam_nn_build.argtypes = [vp, i64, dp, f64, i32p, vp, vp]
+        L.nslam_nn_query.argtypes = [vp, i64, vp, vp, i64, vp, i64, dp, f64, i32p, f64, vp, vp, vp]
+        L.nslam_transform_points.argtypes = [vp, i64, dp, vp, vp]
+        L.nslam_kabsch_sums.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp]
+        L.nslam_kabsch_partials.argtypes = [i64]
+        L.nslam_kabsch_partials.restype = i64
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L

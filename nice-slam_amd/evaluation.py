@@ -1,0 +1,458 @@
+"""Evaluation of a run's output with the reference's tools' call surface (src/tools/cull_mesh.py,
+src/tools/eval_recon.py, src/tools/eval_ate.py), on the HIP kernels of csrc/nslam_eval.hip.
+
+cull_mesh = vertices against every camera's frustum (nslam_frustum_seen) → faces with a seen vertex
+(nslam_mesh_face_cull).  calc_3d_metric = optional point-to-point ICP of the reconstruction's vertices onto the
+ground truth's (nslam_nn_query, nslam_kabsch_sums, a 3x3 SVD on the host) → area-weighted surface samples of both
+meshes (nslam_face_areas, nslam_sample_surface) → accuracy, completion and completion ratio from exact float64
+nearest neighbours (nslam_nn_build / nslam_nn_query).  Torch does allocation, sort, cumsum, searchsorted and
+boolean indexing only; trimesh, open3d and scipy are not imported.  evaluate_ate is n x 3 work and runs on the
+host in float64.
+
+Deviations from the reference, all stated in DESIGN.md §7b:
+  * the samples come from the package's counter-based stream, not numpy's global RNG (same distribution);
+  * icp_align follows open3d's documented point-to-point loop; open3d is absent, so the match with its
+    implementation is unpinned;
+  * calc_2d_metric (depth L1) and the trajectory plot are not built.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import mesher, ops
+
+DEVICE = "cuda:0"
+
+# ------------------------------------------------------------------------------------------------
+# files
+# ------------------------------------------------------------------------------------------------
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",
+              "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4",
+              "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def _ply_header(data, path):
+    if data[:4] != b"ply\n" and data[:5] != b"ply\r\n":
+        raise ValueError(f"{path}: not a PLY file")
+    end = data.find(b"end_header")
+    nl = data.find(b"\n", end)
+    if end < 0 or nl < 0:
+        raise ValueError(f"{path}: the PLY header does not end")
+    fmt, elements = None, []
+    for ln in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        w = ln.split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            elements.append({"name": w[1], "count": int(w[2]), "props": []})
+        elif w[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: a property before any element")
+            try:
+                if w[1] == "list":
+                    elements[-1]["props"].append((w[4], _PLY_TYPES[w[2]], _PLY_TYPES[w[3]]))
+                else:
+                    elements[-1]["props"].append((w[2], _PLY_TYPES[w[1]], None))
+            except (KeyError, IndexError):
+                raise ValueError(f"{path}: unknown property line {ln!r}") from None
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: format {fmt!r} is not read (ascii and binary_little_endian are)")
+    return fmt, elements, nl + 1
+
+
+def _split_faces(rows, path):
+    """Index lists of 3 or 4 → int32 [F,3]; quads are split 0 1 2 / 0 2 3, in place of the quad."""
+    out = []
+    for r in rows:
+        if len(r) == 3:
+            out.append(r)
+        elif len(r) == 4:
+            out.append((r[0], r[1], r[2]))
+            out.append((r[0], r[2], r[3]))
+        else:
+            raise ValueError(f"{path}: a face with {len(r)} indices (3 or 4 are read)")
+    return np.asarray(out, dtype=np.int64).reshape(-1, 3)
+
+
+def _faces_fixed(idx, path):
+    """idx [F,k] with k = 3 or 4 (every face the same size) → [F',3]."""
+    if idx.shape[1] == 3:
+        return idx.astype(np.int64)
+    if idx.shape[1] == 4:
+        return np.stack([idx[:, [0, 1, 2]], idx[:, [0, 2, 3]]], 1).reshape(-1, 3).astype(np.int64)
+    raise ValueError(f"{path}: faces with {idx.shape[1]} indices (3 or 4 are read)")
+
+
+def load_mesh(path):
+    """A PLY triangle or quad mesh → dict(vertices float64 [V,3], faces int32 [F,3], colors uint8 [V,3|4] or None).
+
+    Reads ascii and binary_little_endian files with any scalar vertex properties (x, y, z and red, green, blue
+    [, alpha] are kept; normals and the rest are skipped) and faces `list uchar|uint8 int|uint vertex_indices`
+    (or vertex_index) of 3 or 4 indices; quads are split 0 1 2 / 0 2 3.  A file shorter than its header says,
+    or with an index past the vertices, raises ValueError."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    fmt, elements, pos = _ply_header(data, path)
+    names = [e["name"] for e in elements]
+    if "vertex" not in names:
+        raise ValueError(f"{path}: no vertex element")
+    tokens, tpos = (data[pos:].split(), 0) if fmt == "ascii" else (None, 0)
+    verts = cols = faces = None
+    for e in elements:
+        n, props = e["count"], e["props"]
+        scalar = all(p[2] is None for p in props)
+        if e["name"] == "vertex":
+            pn = [p[0] for p in props]
+            if not scalar or not all(k in pn for k in "xyz"):
+                raise ValueError(f"{path}: the vertex element needs scalar x, y, z")
+            if fmt == "ascii":
+                need = n * len(props)
+                if tpos + need > len(tokens):
+                    raise ValueError(f"{path}: truncated (vertex data)")
+                try:
+                    tab = np.array(tokens[tpos:tpos + need], dtype=np.float64).reshape(n, len(props))
+                except ValueError:
+                    raise ValueError(f"{path}: a vertex value is not a number") from None
+                tpos += need
+                col = {k: tab[:, i] for i, k in enumerate(pn)}
+            else:
+                dt = np.dtype([(f"{k}_{i}", "<" + t) for i, (k, t, _) in enumerate(props)])
+                if pos + n * dt.itemsize > len(data):
+                    raise ValueError(f"{path}: truncated (vertex data)")
+                rec = np.frombuffer(data, dtype=dt, count=n, offset=pos)
+                pos += n * dt.itemsize
+                col = {k: rec[f"{k}_{i}"] for i, k in enumerate(pn)}
+            verts = np.stack([col["x"], col["y"], col["z"]], 1).astype(np.float64)
+            if all(k in col for k in ("red", "green", "blue")):
+                keys = ["red", "green", "blue"] + (["alpha"] if "alpha" in col else [])
+                cols = np.stack([col[k] for k in keys], 1).astype(np.uint8)
+        elif e["name"] == "face":
+            li = [i for i, p in enumerate(props) if p[2] is not None]
+            if len(li) != 1 or props[li[0]][0] not in ("vertex_indices", "vertex_index"):
+                raise ValueError(f"{path}: the face element needs one list property vertex_indices")
+            li = li[0]
+            if fmt == "ascii":
+                rows = []
+                try:
+                    for _ in range(n):
+                        row = None
+                        for i, p in enumerate(props):
+                            if i == li:
+                                k = int(tokens[tpos])
+                                row = tuple(int(t) for t in tokens[tpos + 1:tpos + 1 + k])
+                                if len(row) != k:
+                                    raise IndexError
+                                tpos += 1 + k
+                            else:
+                                tpos += 1
+                        rows.append(row)
+                    if tpos > len(tokens):
+                        raise IndexError
+                except (IndexError, ValueError):
+                    raise ValueError(f"{path}: truncated or malformed (face data)") from None
+                faces = _split_faces(rows, path)
+            else:
+                ct, it = np.dtype("<" + props[li][1]), np.dtype("<" + props[li][2])
+                if ct.kind == "f" or it.kind == "f":
+                    raise ValueError(f"{path}: a face list of floats")
+                if n == 0:
+                    faces = np.zeros((0, 3), np.int64)
+                    continue
+                if pos + ct.itemsize > len(data):
+                    raise ValueError(f"{path}: truncated (face data)")
+                k0 = int(np.frombuffer(data, dtype=ct, count=1, offset=pos)[0])
+                fields = []
+                for i, p in enumerate(props):
+                    fields += [(f"n_{i}", ct), (f"i_{i}", it, (k0,))] if i == li else [(f"s_{i}", "<" + p[1])]
+                dt = np.dtype(fields)
+                rec = None
+                if pos + n * dt.itemsize <= len(data):
+                    rec = np.frombuffer(data, dtype=dt, count=n, offset=pos)
+                    if not (rec[f"n_{li}"] == k0).all():
+                        rec = None
+                if rec is not None:  # every face has k0 indices: one structured read
+                    pos += n * dt.itemsize
+                    faces = _faces_fixed(rec[f"i_{li}"].reshape(n, k0), path)
+                else:                # mixed sizes: face by face
+                    rows = []
+                    for _ in range(n):
+                        row = None
+                        for i, p in enumerate(props):
+                            if i == li:
+                                if pos + ct.itemsize > len(data):
+                                    raise ValueError(f"{path}: truncated (face data)")
+                                k = int(np.frombuffer(data, dtype=ct, count=1, offset=pos)[0])
+                                pos += ct.itemsize
+                                if pos + k * it.itemsize > len(data):
+                                    raise ValueError(f"{path}: truncated (face data)")
+                                row = tuple(int(v) for v in np.frombuffer(data, dtype=it, count=k, offset=pos))
+                                pos += k * it.itemsize
+                            else:
+                                pos += np.dtype(p[1]).itemsize
+                        rows.append(row)
+                    if pos > len(data):
+                        raise ValueError(f"{path}: truncated (face data)")
+                    faces = _split_faces(rows, path)
+        else:  # an element this reader has no use for: skipped when its size is known
+            if not scalar:
+                raise ValueError(f"{path}: element {e['name']!r} has list properties; it cannot be skipped")
+            if fmt == "ascii":
+                tpos += n * len(props)
+                if tpos > len(tokens):
+                    raise ValueError(f"{path}: truncated ({e['name']} data)")
+            else:
+                pos += n * sum(np.dtype(p[1]).itemsize for p in props)
+                if pos > len(data):
+                    raise ValueError(f"{path}: truncated ({e['name']} data)")
+    if faces is None:
+        faces = np.zeros((0, 3), np.int64)
+    if faces.size and (faces.min() < 0 or faces.max() >= verts.shape[0]):
+        raise ValueError(f"{path}: a face indexes past the {verts.shape[0]} vertices")
+    return {"vertices": verts, "faces": faces.astype(np.int32), "colors": cols}
+
+
+def load_poses(path):
+    """cull_mesh.py:9-19: one 4x4 camera-to-world matrix per line (16 numbers), the y and z columns of its
+    rotation negated, cast to float32 → numpy float32 [N,4,4]."""
+    poses = []
+    with open(path, "r") as f:
+        lines = f.readlines()
+    for line in lines:
+        if not line.strip():
+            continue
+        c2w = np.array(list(map(float, line.split()))).reshape(4, 4)
+        c2w[:3, 1] *= -1
+        c2w[:3, 2] *= -1
+        poses.append(c2w.astype(np.float32))
+    return np.stack(poses, 0) if poses else np.zeros((0, 4, 4), np.float32)
+
+
+def _dev64(x, device=None):
+    """Array or tensor → contiguous float64 tensor on the HIP device."""
+    if isinstance(x, torch.Tensor):
+        dev = x.device if x.is_cuda and device is None else (device or DEVICE)
+        return x.detach().to(device=dev, dtype=torch.float64).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64))).to(device or DEVICE)
+
+
+def _faces32(faces, device):
+    if isinstance(faces, torch.Tensor):
+        return faces.detach().to(device=device, dtype=torch.int32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(faces, dtype=np.int32))).to(device)
+
+
+# ------------------------------------------------------------------------------------------------
+# cull_mesh
+# ------------------------------------------------------------------------------------------------
+def seen_vertices(vertices, poses, H=680, W=1200, fx=600., fy=600., cx=599.5, cy=339.5, device=None):
+    """bool [V] on the device: the vertex lies in some camera's viewing frustum (cull_mesh.py:47-71).
+    poses: float32 camera-to-world matrices [N,4,4] as load_poses returns them; inverted here on the host in
+    float32, as the reference does."""
+    v = _dev64(vertices, device)
+    poses = np.asarray(poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else poses, dtype=np.float32)
+    poses = poses.reshape(-1, 4, 4)
+    w2c = np.stack([np.linalg.inv(p).astype(np.float32) for p in poses], 0) if len(poses) else \
+        np.zeros((0, 4, 4), np.float32)
+    return ops.frustum_seen(v, torch.from_numpy(w2c).to(v.device).contiguous(), H, W, fx, fy, cx, cy)
+
+
+def cull_mesh(mesh, poses, H=680, W=1200, fx=600., fy=600., cx=599.5, cy=339.5, device=None):
+    """cull_mesh.py: drop the faces whose three vertices are all outside every camera's frustum.  mesh: the dict
+    load_mesh returns; the result is such a dict with the vertex array (and colours) unchanged, as trimesh's
+    update_faces leaves them."""
+    seen = seen_vertices(mesh["vertices"], poses, H, W, fx, fy, cx, cy, device)
+    faces = _faces32(mesh["faces"], seen.device)
+    keep = ops.mesh_face_cull(faces, ~seen)
+    out = dict(mesh)
+    out["faces"] = faces[keep].cpu().numpy()
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# 3D reconstruction metrics
+# ------------------------------------------------------------------------------------------------
+def sample_surface(vertices, faces, count, seed, device=None):
+    """trimesh.sample.sample_surface on the device → (points float64 [count,3], face_id int32 [count])."""
+    v = _dev64(vertices, device)
+    pts, fid, _ = ops.sample_surface(v, _faces32(faces, v.device), count, seed)
+    return pts, fid
+
+
+def nn_distance(query, target, max_dist=None, device=None):
+    """Exact nearest neighbour of every query among the targets → (dist float64 [N], idx int32 [N]) on the
+    device; beyond max_dist: inf and -1.  `target` may be an ops.NNGrid built earlier."""
+    if isinstance(target, ops.NNGrid):
+        grid = target
+        q = _dev64(query, grid.sorted.device)
+    else:
+        t = _dev64(target, device)
+        grid = ops.NNGrid(t)
+        q = _dev64(query, t.device)
+    return grid.query(q, max_dist)
+
+
+def completion_ratio(gt_points, rec_points, dist_th=0.05):
+    d, _ = nn_distance(gt_points, rec_points)
+    return float((d < dist_th).to(torch.float64).mean())
+
+
+def accuracy(gt_points, rec_points):
+    d, _ = nn_distance(rec_points, gt_points)
+    return float(d.mean())
+
+
+def completion(gt_points, rec_points):
+    d, _ = nn_distance(gt_points, rec_points)
+    return float(d.mean())
+
+
+def _kabsch(s):
+    """The rigid update (4x4, float64 numpy) that moves the a's onto the b's, from nslam_kabsch_sums' totals."""
+    n = s[0]
+    sa, sb, sab = s[1:4], s[4:7], s[7:16].reshape(3, 3)
+    mu_a, mu_b = sa / n, sb / n
+    m = sab - np.outer(sa, sb) / n                      # Σ (a - μa)(b - μb)ᵀ
+    u, _, vh = torch.linalg.svd(torch.from_numpy(m))
+    u, vh = u.numpy(), vh.numpy()
+    d = np.eye(3)
+    if np.linalg.det(vh.T @ u.T) < 0:
+        d[2, 2] = -1.0
+    r = vh.T @ d @ u.T
+    t = np.eye(4)
+    t[:3, :3] = r
+    t[:3, 3] = mu_b - r @ mu_a
+    return t
+
+
+def icp_align(src_vertices, dst_vertices, threshold=0.1, max_iteration=30, relative_fitness=1e-6,
+              relative_rmse=1e-6, device=None):
+    """Point-to-point ICP of src onto dst from the identity (get_align_transformation, eval_recon.py:45-59:
+    open3d's registration_icp with its default criteria) → 4x4 float64 numpy matrix.
+
+    The loop is open3d's as documented: correspondences = nearest target within `threshold` of the transformed
+    source, fitness = matched share, inlier RMSE; stop when both change by less than their criterion; else the
+    Kabsch update of the matched pairs.  The target grid is built once; every iteration reads 17 sums back."""
+    dst = _dev64(dst_vertices, device)
+    src = _dev64(src_vertices, dst.device)
+    grid = ops.NNGrid(dst)
+    trans = np.eye(4)
+    n = src.shape[0]
+
+    def register(cur):
+        _, idx = grid.query(cur, threshold)
+        s = ops.kabsch_sums(cur, idx, dst)
+        fit = s[0] / n if n else 0.0
+        rmse = float(np.sqrt(s[16] / s[0])) if s[0] > 0 else 0.0
+        return s, fit, rmse
+
+    cur = src
+    s, fit, rmse = register(cur)
+    for _ in range(int(max_iteration)):
+        if s[0] < 3:  # no update can be formed
+            break
+        trans = _kabsch(s) @ trans
+        cur = ops.transform_points(src, trans)
+        s_new, fit_new, rmse_new = register(cur)
+        done = abs(fit - fit_new) < relative_fitness and abs(rmse - rmse_new) < relative_rmse
+        s, fit, rmse = s_new, fit_new, rmse_new
+        if done:
+            break
+    return trans
+
+
+def calc_3d_metric(rec_meshfile, gt_meshfile, align=True, n_points=200000, seed=0, device=None):
+    """eval_recon.py:91-117 → {accuracy_cm, completion_cm, completion_ratio_pct}, printed as the reference
+    prints them.  The reconstruction is sampled with `seed`, the ground truth with `seed + 1`."""
+    rec, gt = load_mesh(rec_meshfile), load_mesh(gt_meshfile)
+    rec_v, gt_v = _dev64(rec["vertices"], device), _dev64(gt["vertices"], device)
+    if align:
+        rec_v = ops.transform_points(rec_v, icp_align(rec_v, gt_v))
+    rec_pc, _ = sample_surface(rec_v, rec["faces"], n_points, seed)
+    gt_pc, _ = sample_surface(gt_v, gt["faces"], n_points, seed + 1)
+    gt_grid, rec_grid = ops.NNGrid(gt_pc), ops.NNGrid(rec_pc)
+    d_acc, _ = gt_grid.query(rec_pc)
+    d_comp, _ = rec_grid.query(gt_pc)
+    out = {"accuracy_cm": float(d_acc.mean()) * 100, "completion_cm": float(d_comp.mean()) * 100,
+           "completion_ratio_pct": float((d_comp < 0.05).to(torch.float64).mean()) * 100}
+    print('accuracy: ', out["accuracy_cm"])
+    print('completion: ', out["completion_cm"])
+    print('completion ratio: ', out["completion_ratio_pct"])
+    return out
+
+
+def calc_2d_metric(*args, **kwargs):
+    raise NotImplementedError("the 2D depth-L1 metric is not built: it needs a mesh rasteriser, oriented bounds and "
+                              "the dataset's _pc_unseen.npy (DESIGN §7b)")
+
+
+# ------------------------------------------------------------------------------------------------
+# ATE (host, float64)
+# ------------------------------------------------------------------------------------------------
+def convert_poses(c2w_list, N, scale, gt=True):
+    """eval_ate.py:239-256 → (translations [M,3] = c2w[:3,3] / scale of frames 0..N, mask bool [N+1]).
+    With gt, poses holding NaN or inf are masked out.  The input is not modified (the reference divides in
+    place), and only the translation is kept: evaluate_ate reads nothing else of the reference's 7-vector."""
+    poses = []
+    mask = torch.ones(N + 1).bool()
+    for idx in range(0, N + 1):
+        c2w = torch.as_tensor(c2w_list[idx])
+        if gt and (torch.isinf(c2w).any() or torch.isnan(c2w).any()):
+            mask[idx] = 0
+            continue
+        poses.append(c2w[:3, 3] / scale)
+    poses = torch.stack(poses) if poses else torch.zeros(0, 3)
+    return poses, mask
+
+
+def align_horn(model, data):
+    """eval_ate.py:44-78: the closed-form (Horn) rigid alignment of model [3,n] onto data [3,n] →
+    (rot [3,3], trans [3,1], trans_error [n])."""
+    model, data = np.asarray(model, dtype=np.float64), np.asarray(data, dtype=np.float64)
+    mm, dm = model.mean(1, keepdims=True), data.mean(1, keepdims=True)
+    mz, dz = model - mm, data - dm
+    u, _, vh = np.linalg.svd((mz @ dz.T).transpose())   # Σ outer(model_c, data_c) over the frames, transposed
+    s = np.identity(3)
+    if np.linalg.det(u) * np.linalg.det(vh) < 0:
+        s[2, 2] = -1
+    rot = u @ s @ vh
+    trans = dm - rot @ mm
+    err = rot @ model + trans - data
+    return rot, trans, np.sqrt(np.sum(np.multiply(err, err), 0))
+
+
+def evaluate_ate(poses_gt, poses_est):
+    """eval_ate.py:113-236 for two trajectories with the same frames ([n, >=3], the translation first) → the
+    reference's result dict (ATE after Horn alignment of the estimate onto the ground truth, metres)."""
+    def xyz(p):
+        p = p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)
+        return np.asarray(p, dtype=np.float64).reshape(p.shape[0], -1)[:, :3].T
+    first, second = xyz(poses_gt), xyz(poses_est)
+    if first.shape != second.shape:
+        raise ValueError("evaluate_ate: the trajectories differ in length")
+    if first.shape[1] < 2:
+        raise ValueError("evaluate_ate: fewer than two pose pairs to compare")
+    _, _, e = align_horn(second, first)
+    return {
+        "compared_pose_pairs": len(e),
+        "absolute_translational_error.rmse": np.sqrt(np.dot(e, e) / len(e)),
+        "absolute_translational_error.mean": np.mean(e),
+        "absolute_translational_error.median": np.median(e),
+        "absolute_translational_error.std": np.std(e),
+        "absolute_translational_error.min": np.min(e),
+        "absolute_translational_error.max": np.max(e),
+    }
+
+
+def evaluate_ate_checkpoint(ckpt, scale):
+    """The ATE dict of a checkpoint dict (datasets.load_checkpoint): frames 0..ckpt['idx'], invalid ground-truth
+    poses masked out of both trajectories (eval_ate.py:286-301)."""
+    n = int(ckpt["idx"])
+    poses_gt, mask = convert_poses(ckpt["gt_c2w_list"], n, scale)
+    poses_est, _ = convert_poses(ckpt["estimate_c2w_list"], n, scale, gt=False)
+    return evaluate_ate(poses_gt, poses_est[mask])
+
+
+write_ply = mesher.write_ply
