@@ -527,7 +527,8 @@ int nslam_mesh_select(const int32_t* faces, int64_t n_faces, const int32_t* labe
 int nslam_mesh_remap(const int32_t* faces, int64_t n_faces, const int32_t* new_id, int32_t* out, void* stream);
 
 /* Evaluation (src/tools/cull_mesh.py, src/tools/eval_recon.py; csrc/nslam_eval.hip); additive, no ABI bump.
- * No entry point here uses atomics: every output is the same from run to run.
+ * No entry point here uses atomics, with one exception: nslam_raster_depth combines its hits with an integer
+ * atomicMin, which does not depend on the order.  Every output is the same from run to run.
  *
  * seen[i] = 1 when vertex i (float64 [n][3], cast to float32 as the reference does) projects into the image
  * of any of n_frames cameras (cull_mesh.py:47-71, eval_recon.py:62-88).  w2c: device float32 [n_frames][16],
@@ -580,6 +581,44 @@ int nslam_transform_points(const double* pts, int64_t n, const double* rigid, do
 int nslam_kabsch_sums(const double* src, const int32_t* idx, int64_t n, const double* targets, int64_t m,
                       double* partials, int64_t n_partials, void* stream);
 int64_t nslam_kabsch_partials(int64_t n);
+
+/* Depth L1 of eval_recon.py's calc_2d_metric (:131-210; csrc/nslam_raster.hip, csrc/nslam_eval.hip); additive.
+ *
+ * any[b] = 1 when some point of the cloud (float64 [n][3]) passes view b's frustum test: nslam_frustum_seen's
+ * test and arithmetic with the roles swapped (check_proj: many views, one cloud).  w2c float32 [n_views][16].
+ * The kernel only ever stores 1: the caller zeroes `any` (uint8 [n_views]).  At most 65535 views per call. */
+int nslam_views_see_any(const double* pts, int64_t n, const float* w2c, int32_t n_views, int32_t H, int32_t W,
+                        float fx, float fy, float cx, float cy, uint8_t* any, void* stream);
+/* out[b] = mean over the n_pix pixels of view b of |a - b| (float32 [n_views][n_pix] each), float64: per-thread
+ * sums in pixel order, __shfl_down over the wave, one LDS step; no atomics.  Background pixels count. */
+int nslam_depth_l1(const float* a, const float* b, int64_t n_views, int64_t n_pix, double* out, void* stream);
+
+/* depth float32 [n_views][H][W]: pixel (u, v) gets the camera-space z (not the ray length) of the nearest
+ * intersection of the ray through its centre, direction ((u - cx) / fx, (v - cy) / fy, 1), with any triangle of
+ * the mesh (verts float64 [n_verts][3], faces int32 [n_faces][3]); 0 where nothing is hit.  w2c: device float64
+ * [n_views][12], the row-major [3][4] world-to-camera matrix of a camera that looks along +z with x right and
+ * y down.  Only hits with z_near < z <= z_far count, per pixel (a triangle that crosses the near plane draws
+ * its part in front of it); both sides of a triangle are visible; edges are inclusive.  A face with zero area,
+ * a non-finite vertex or an index outside the vertices draws nothing.
+ * The vertex transform and the intersection are float64 without FMA contraction; z is rounded to float32 once
+ * and combined with atomicMin on its bits, so the image is bit-identical from run to run, for every
+ * small_max_pixels and every workspace size.
+ * Passes (separate launches on the stream; NSLAM_RASTER_ALL runs them in order): CLEAR sets the image to +inf
+ * and empties the list; SMALL runs one thread per (face, view), which tests a pixel box of at most
+ * small_max_pixels pixels itself and appends a larger one to the list in the workspace (when the list is full
+ * it tests that box itself too: nothing is dropped); BIG gives every listed item a workgroup; RESOLVE writes 0
+ * for +inf.  The workspace size function gives the bytes for a list of `capacity` items (at least 1); a larger
+ * workspace holds a longer list.
+ * n_views == 0 or n_faces == 0: NSLAM_OK without a launch (depth is not written).  NSLAM_EINVAL: a negative
+ * count, H, W, fx or fy not positive, z_near < 0, z_near >= z_far, small_max_pixels < 0, a null pointer, a
+ * workspace shorter than that of one item.  NSLAM_EUNSUPPORTED: more than 65535 views in one call. */
+enum { NSLAM_RASTER_CLEAR = 1, NSLAM_RASTER_SMALL = 2, NSLAM_RASTER_BIG = 4, NSLAM_RASTER_RESOLVE = 8,
+       NSLAM_RASTER_ALL = 15 };
+int nslam_raster_depth(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                       const double* w2c, int32_t n_views, int32_t H, int32_t W, double fx, double fy, double cx,
+                       double cy, double z_near, double z_far, int64_t small_max_pixels, int32_t passes,
+                       float* depth, void* ws, size_t ws_bytes, void* stream);
+size_t nslam_raster_workspace_size(int64_t capacity);
 
 enum { NSLAM_WS_SAMPLER = 0 };
 size_t nslam_workspace_size(int which, int64_t n);

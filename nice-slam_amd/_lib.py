@@ -138,6 +138,8 @@ EXPORTS = (
     # evaluation: frustum culling, surface samples, nearest neighbours, ICP sums (additive: no ABI bump)
     "nslam_frustum_seen", "nslam_face_areas", "nslam_sample_surface", "nslam_nn_build", "nslam_nn_query",
     "nslam_transform_points", "nslam_kabsch_sums", "nslam_kabsch_partials",
+    # depth L1: mesh rasteriser, view rejection, per-view error (additive: no ABI bump)
+    "nslam_raster_depth", "nslam_raster_workspace_size", "nslam_views_see_any", "nslam_depth_l1",
 )
 
 _lib = None
@@ -239,6 +241,12 @@ def lib():
         L.nslam_kabsch_sums.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp]
         L.nslam_kabsch_partials.argtypes = [i64]
         L.nslam_kabsch_partials.restype = i64
+        L.nslam_raster_depth.argtypes = [vp, i64, vp, i64, vp, i32, i32, i32, f64, f64, f64, f64, f64, f64, i64, i32,
+                                         vp, vp, sz, vp]
+        L.nslam_raster_workspace_size.argtypes = [i64]
+        L.nslam_raster_workspace_size.restype = sz
+        L.nslam_views_see_any.argtypes = [vp, i64, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp]
+        L.nslam_depth_l1.argtypes = [vp, vp, i64, i64, vp, vp]
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L

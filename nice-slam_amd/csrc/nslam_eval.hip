@@ -1,12 +1,15 @@
 // nslam_eval.hip — the per-vertex, per-face and per-point work of the evaluation tools (src/tools/cull_mesh.py,
 // src/tools/eval_recon.py):
 //   nslam_frustum_seen        vertices inside any camera's viewing frustum (cull_mesh.py:47-71, check_proj)
+//   nslam_views_see_any       the same test per view: does the view see any point of a cloud (eval_recon.py:176)
+//   nslam_depth_l1            per-view mean |a - b| of two depth-image batches (eval_recon.py:206)
 //   nslam_face_areas / nslam_sample_surface   area-weighted surface samples (replaces trimesh.sample.sample_surface)
 //   nslam_nn_build / nslam_nn_query           exact float64 nearest neighbours on a uniform cell grid (replaces
 //                                             scipy's cKDTree and open3d's correspondence search)
 //   nslam_transform_points / nslam_kabsch_sums / nslam_kabsch_partials   the per-point half of point-to-point ICP
 // Latency-bound elementwise work: one thread per vertex, sample or query, wave-uniform matrices and grid
-// parameters, global_* loads (as_global), no atomics.  The build has -ffp-contract=off: the float32 projection
+// parameters, global_* loads (as_global), no atomics (the one exception in the evaluation module is the depth
+// rasteriser's integer atomicMin, nslam_raster.hip: order-independent, so still the same from run to run).  The build has -ffp-contract=off: the float32 projection
 // rounds where the reference's torch ops round and the float64 sampler where its numpy restatement rounds.
 #include <math.h>
 
@@ -66,6 +69,37 @@ __global__ __launch_bounds__(kEvalThreads) void k_frustum_seen(SeenArgs a) {
     seen = frustum_test(a, as_global(a.w2c) + 16 * k, x, y, z);  // k is wave-uniform: scalar loads
   }
   if (live) a.seen[i] = seen ? 1 : 0;
+}
+
+// check_proj with the roles swapped (eval_recon.py:62-88: many views, one cloud): any[view] = 1 when some point
+// passes the view's frustum_test.  Grid (chunk of points, view); a wave with a hit stores one byte of 1 — every
+// writer stores the same value, so the plain stores race benignly.  a.seen is [K] here and zeroed by the caller.
+__global__ __launch_bounds__(kEvalThreads) void k_views_see_any(SeenArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * kEvalThreads + threadIdx.x;
+  const int32_t view = blockIdx.y;  // wave-uniform: scalar loads of the matrix
+  bool hit = false;
+  if (i < a.n) {
+    const gptr_t<double> p = as_global(a.verts) + 3 * i;
+    hit = frustum_test(a, as_global(a.w2c) + 16 * (int64_t)view, (float)p[0], (float)p[1], (float)p[2]);
+  }
+  if (__ballot(hit) != 0 && (threadIdx.x & 63) == 0) a.seen[view] = 1;
+}
+
+// out[view] = mean |a - b| over the view's n_pix pixels in float64: every thread adds its pixels in order, then
+// __shfl_down over the wave, then the waves in order through LDS (k_kabsch_sums' pattern) — the same sum every run
+__global__ __launch_bounds__(kEvalThreads) void k_depth_l1(const float* a, const float* b, int64_t n_pix, double* out) {
+  __shared__ double part[kEvalThreads / 64];
+  const gptr_t<float> ga = as_global(a) + (int64_t)blockIdx.x * n_pix, gb = as_global(b) + (int64_t)blockIdx.x * n_pix;
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n_pix; i += kEvalThreads) s += fabs((double)ga[i] - (double)gb[i]);
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = part[0];
+    for (int w = 1; w < kEvalThreads / 64; ++w) t += part[w];
+    out[blockIdx.x] = t / (double)n_pix;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -332,6 +366,40 @@ extern "C" int nslam_frustum_seen(const double* verts, int64_t n, const float* w
   a.seen = seen;
   hipLaunchKernelGGL(k_frustum_seen, dim3((unsigned)blocks_for(n)), dim3(kEvalThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
+  return hip_status();
+}
+
+extern "C" int nslam_views_see_any(const double* pts, int64_t n, const float* w2c, int32_t n_views, int32_t H,
+                                   int32_t W, float fx, float fy, float cx, float cy, uint8_t* any, void* stream) {
+  if (n < 0 || n_views < 0 || H <= 0 || W <= 0) return NSLAM_EINVAL;
+  if (n == 0 || n_views == 0) return NSLAM_OK;  // nothing can be seen: `any` stays as the caller zeroed it
+  if (!pts || !w2c || !any) return NSLAM_EINVAL;
+  if (blocks_for(n) >= (int64_t(1) << 31) || n_views > 65535) return NSLAM_EUNSUPPORTED;
+  SeenArgs a{};
+  a.verts = pts;
+  a.w2c = w2c;
+  a.n = n;
+  a.K = n_views;
+  a.H = H;
+  a.W = W;
+  a.fx = fx;
+  a.fy = fy;
+  a.cx = cx;
+  a.cy = cy;
+  a.seen = any;
+  hipLaunchKernelGGL(k_views_see_any, dim3((unsigned)blocks_for(n), (unsigned)n_views), dim3(kEvalThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  return hip_status();
+}
+
+extern "C" int nslam_depth_l1(const float* a, const float* b, int64_t n_views, int64_t n_pix, double* out,
+                              void* stream) {
+  if (n_views < 0 || n_pix < 0) return NSLAM_EINVAL;
+  if (n_views == 0) return NSLAM_OK;
+  if (n_pix == 0 || !a || !b || !out) return NSLAM_EINVAL;  // the mean of no pixels
+  if (n_views >= (int64_t(1) << 31)) return NSLAM_EUNSUPPORTED;
+  hipLaunchKernelGGL(k_depth_l1, dim3((unsigned)n_views), dim3(kEvalThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), a, b, n_pix, out);
   return hip_status();
 }
 

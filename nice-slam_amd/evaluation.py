@@ -6,14 +6,21 @@ cull_mesh = vertices against every camera's frustum (nslam_frustum_seen) → fac
 ground truth's (nslam_nn_query, nslam_kabsch_sums, a 3x3 SVD on the host) → area-weighted surface samples of both
 meshes (nslam_face_areas, nslam_sample_surface) → accuracy, completion and completion ratio from exact float64
 nearest neighbours (nslam_nn_build / nslam_nn_query).  Torch does allocation, sort, cumsum, searchsorted and
-boolean indexing only; trimesh, open3d and scipy are not imported.  evaluate_ate is n x 3 work and runs on the
-host in float64.
+boolean indexing only; trimesh and open3d are not imported, scipy only by oriented_bounds.  evaluate_ate is n x 3
+work and runs on the host in float64.  calc_depth_l1 (the reference's calc_2d_metric) = views drawn inside the
+ground truth's shrunk oriented box and rejected when they see an unseen point (nslam_views_see_any) → both meshes
+rendered from each (nslam_raster_depth, csrc/nslam_raster.hip) → the mean absolute depth difference
+(nslam_depth_l1).
 
 Deviations from the reference, all stated in DESIGN.md §7b:
   * the samples come from the package's counter-based stream, not numpy's global RNG (same distribution);
   * icp_align follows open3d's documented point-to-point loop; open3d is absent, so the match with its
     implementation is unpinned;
-  * calc_2d_metric (depth L1) and the trajectory plot are not built.
+  * calc_depth_l1 renders with the package's rasteriser (pixel-centre rays, inclusive edges) in place of an
+    open3d OpenGL window, draws its views from the counter-based stream, takes the near plane as a parameter and
+    restates trimesh's oriented bounds (scipy's ConvexHull, imported lazily); open3d and trimesh are absent, so
+    the match with them is unpinned;
+  * the trajectory plot is not built.
 """
 from __future__ import annotations
 
@@ -384,8 +391,260 @@ def calc_3d_metric(rec_meshfile, gt_meshfile, align=True, n_points=200000, seed=
 
 
 def calc_2d_metric(*args, **kwargs):
-    raise NotImplementedError("the 2D depth-L1 metric is not built: it needs a mesh rasteriser, oriented bounds and "
-                              "the dataset's _pc_unseen.npy (DESIGN §7b)")
+    raise NotImplementedError("calc_2d_metric is not an entry point of this package: the 2D depth-L1 metric is "
+                              "calc_depth_l1 (seeded views, the near plane as a parameter; DESIGN §7b)")
+
+
+# ------------------------------------------------------------------------------------------------
+# 2D metric: depth L1 (eval_recon.py:120-210)
+# ------------------------------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+VIEW_BATCH_BYTES = 256 << 20     # two float32 image batches (ground truth, reconstruction) stay under this
+
+
+def _mix64(x):
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
+    return x ^ (x >> np.uint64(31))
+
+
+def _uniforms(seed, first, count, k):
+    """Uniform k of the draws first..first+count-1 in [0,1): the counter-based stream of nslam_sample_surface,
+    (mix64(seed ^ mix64(i * 0x9e3779b97f4a7c15 + k)) >> 11) * 2^-53, on the host."""
+    with np.errstate(over="ignore"):
+        i = np.arange(first, first + count, dtype=np.uint64)
+        bits = _mix64(np.uint64(int(seed) & _M64) ^ _mix64(i * np.uint64(0x9e3779b97f4a7c15) + np.uint64(k)))
+    return (bits >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def _hull_2d(p):
+    """Indices of the convex hull of 2D points, counter-clockwise (Andrew's monotone chain)."""
+    order = np.lexsort((p[:, 1], p[:, 0]))
+    def half(idx):
+        h = []
+        for i in idx:
+            while len(h) >= 2:
+                a, b = p[h[-2]], p[h[-1]]
+                if (b[0] - a[0]) * (p[i][1] - a[1]) - (b[1] - a[1]) * (p[i][0] - a[0]) > 0.0:
+                    break
+                h.pop()
+            h.append(i)
+        return h
+    lo, hi = half(order), half(order[::-1])
+    return np.array(lo[:-1] + hi[:-1], dtype=np.int64)
+
+
+def _min_rectangle(p):
+    """The minimum-area rectangle round 2D points → (area, angle of its first axis, lo [2], hi [2] along its
+    axes): one candidate per edge of the convex hull."""
+    h = p[_hull_2d(p)] if len(p) > 2 else p
+    edges = np.roll(h, -1, 0) - h
+    norm = np.linalg.norm(edges, axis=1)
+    edges = edges[norm > 0.0] / norm[norm > 0.0][:, None]
+    if len(edges) == 0:
+        edges = np.array([[1.0, 0.0]])
+    best = None
+    for e in edges:
+        x = h @ e
+        y = h @ np.array([-e[1], e[0]])
+        area = (x.max() - x.min()) * (y.max() - y.min())
+        if best is None or area < best[0]:
+            best = (area, e, np.array([x.min(), y.min()]), np.array([x.max(), y.max()]))
+    return best
+
+
+def oriented_bounds(vertices):
+    """The minimum-volume oriented box of a point set (trimesh.bounds.oriented_bounds) → (to_origin float64
+    [4,4], extents float64 [3]): to_origin moves the points into the box -extents/2 .. extents/2, extents ascending,
+    the rotation right-handed.  Host, float64: one candidate per face normal of the convex hull (its height along
+    the normal times the minimum-area rectangle in the face's plane).  trimesh is absent: ties between candidates
+    and the signs of the axes are this function's own."""
+    try:
+        from scipy.spatial import ConvexHull
+    except ImportError as e:
+        raise ImportError("evaluation.oriented_bounds needs scipy (scipy.spatial.ConvexHull); install it, or pass "
+                          "calc_depth_l1(..., cam_box=(extents, transform))") from e
+    v = np.asarray(vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else vertices,
+                   dtype=np.float64).reshape(-1, 3)
+    v = v[np.isfinite(v).all(1)]
+    hull = ConvexHull(v)
+    hv = v[hull.vertices]
+    normals = hull.equations[:, :3]
+    # one candidate per distinct direction (a normal and its negation give the same box)
+    keys = np.round(normals * np.where(normals[:, [np.argmax(np.abs(normals).sum(0) > 0)]] < 0, -1.0, 1.0), 9)
+    _, first = np.unique(keys, axis=0, return_index=True)
+    best = None
+    for n in normals[np.sort(first)]:
+        n = n / np.linalg.norm(n)
+        a = np.eye(3)[np.argmin(np.abs(n))]
+        u = np.cross(n, a)
+        u /= np.linalg.norm(u)
+        w = np.cross(n, u)
+        area, e, lo2, hi2 = _min_rectangle(np.stack([hv @ u, hv @ w], 1))
+        z = hv @ n
+        vol = area * (z.max() - z.min())
+        if best is None or vol < best[0]:
+            ax0 = e[0] * u + e[1] * w
+            ax1 = -e[1] * u + e[0] * w
+            best = (vol, np.stack([ax0, ax1, n]), np.array([lo2[0], lo2[1], z.min()]),
+                    np.array([hi2[0], hi2[1], z.max()]))
+    _, rot, lo, hi = best
+    ext = hi - lo
+    order = np.argsort(ext, kind="stable")
+    rot, lo, hi, ext = rot[order], lo[order], hi[order], ext[order]
+    if np.linalg.det(rot) < 0.0:      # keep it a rotation: turn the last axis round
+        rot[2] = -rot[2]
+        lo[2], hi[2] = -hi[2], -lo[2]
+    to_origin = np.eye(4)
+    to_origin[:3, :3] = rot
+    to_origin[:3, 3] = -(lo + hi) / 2.0
+    return to_origin, ext
+
+
+def get_cam_position(gt_vertices):
+    """eval_recon.py:120-128 → (extents [3], transform [4,4]): the box the cameras are drawn from, the oriented
+    bounds shrunk to (0.3, 0.7, 0.7) of their extents, moved back into the world and lifted 0.4 along world z."""
+    to_origin, extents = oriented_bounds(gt_vertices)
+    extents = extents * np.array([0.3, 0.7, 0.7])
+    transform = np.linalg.inv(to_origin)
+    transform[2, 3] += 0.4
+    return extents, transform
+
+
+def _viewmatrix(z, up, pos):
+    """eval_recon.py:15-21, for a batch: [n,3,4] = (x, y, z, position) columns."""
+    vec2 = z / np.linalg.norm(z, axis=1, keepdims=True)
+    vec0 = np.cross(np.broadcast_to(up, vec2.shape), vec2)
+    vec0 /= np.linalg.norm(vec0, axis=1, keepdims=True)
+    vec1 = np.cross(vec2, vec0)
+    vec1 /= np.linalg.norm(vec1, axis=1, keepdims=True)
+    return np.stack([vec0, vec1, vec2, pos], 2)
+
+
+def _check_proj_w2c(c2w):
+    """check_proj's matrices (eval_recon.py:67-72): y and z columns negated, float64 inverse, float32 cast."""
+    m = c2w.copy()
+    m[:, :3, 1] *= -1.0
+    m[:, :3, 2] *= -1.0
+    return np.linalg.inv(m).astype(np.float32) if len(m) else np.zeros((0, 4, 4), np.float32)
+
+
+def sample_views(n, extents, transform, unseen_pc, seed, H=500, W=500, fx=300., fy=300., cx=249.5, cy=249.5,
+                 batch=None, device=None):
+    """The views of calc_2d_metric's loop (eval_recon.py:159-178) → float64 numpy [n,4,4] camera-to-world.
+
+    Candidate i draws six uniforms from the counter-based stream (seed, i, k): its origin is uniform in the box
+    ((u - 1/2) * extents, then `transform`: trimesh.sample.volume_rectangular), its target has each coordinate
+    uniform in +-10000 rounded to two decimals, its pose is viewmatrix(target - origin, (0, 0, -1), origin).  A
+    candidate whose image holds a point of unseen_pc (check_proj) is rejected; the result is the first n accepted
+    candidates in candidate order, so it depends on the seed and not on `batch` (candidates tested per launch).
+    After 64 n candidates without n accepted: RuntimeError (the reference would loop for ever)."""
+    n = int(n)
+    extents = np.asarray(extents, dtype=np.float64).reshape(3)
+    transform = np.asarray(transform, dtype=np.float64).reshape(4, 4)
+    pc = None
+    if unseen_pc is not None and len(unseen_pc):
+        pc = _dev64(unseen_pc, device).reshape(-1, 3).contiguous()
+    batch = max(1, int(batch) if batch else max(64, 2 * n))
+    up = np.array([0.0, 0.0, -1.0])
+    kept, have, first, limit = [], 0, 0, 64 * n
+    while have < n:
+        if first >= limit:
+            raise RuntimeError(f"sample_views: {limit} candidates gave only {have} of {n} views that see no unseen "
+                               "point; the camera box or the unseen cloud does not fit this mesh")
+        m = min(batch, limit - first)
+        u = np.stack([_uniforms(seed, first, m, k) for k in range(6)], 1)
+        origin = ((u[:, :3] - 0.5) * extents) @ transform[:3, :3].T + transform[:3, 3]
+        target = np.round(u[:, 3:] * 20000.0 - 10000.0, 2)
+        c2w = np.tile(np.eye(4), (m, 1, 1))
+        c2w[:, :3, :] = _viewmatrix(target - origin, up, origin)
+        if pc is None:
+            ok = np.ones(m, dtype=bool)
+        else:
+            w2c = torch.from_numpy(_check_proj_w2c(c2w)).to(pc.device).contiguous()
+            ok = ~ops.views_see_any(pc, w2c, H, W, fx, fy, cx, cy).cpu().numpy()
+        kept.append(c2w[ok][:n - have])
+        have += len(kept[-1])
+        first += m
+    return np.concatenate(kept, 0) if kept else np.zeros((0, 4, 4))
+
+
+def render_depth(vertices, faces, c2w=None, *, w2c=None, H=500, W=500, fx=300., fy=300., cx=249.5, cy=249.5,
+                 z_near=0.01, z_far=20., small_max_pixels=None, device=None):
+    """Depth images of a mesh (nslam_raster_depth) → float32 [B,H,W] on the device: the camera-space z of the
+    nearest triangle at every pixel centre, 0 for background — what open3d's capture_depth_float_buffer(True)
+    returns with mesh_show_back_face.  Give the cameras as c2w (camera-to-world; inverted here in float64, as
+    eval_recon.py:181 does) or as w2c = param.extrinsic; [B,4,4], the camera looks along +z with y down."""
+    if (c2w is None) == (w2c is None):
+        raise ValueError("render_depth: give c2w or w2c (one of them)")
+    v = _dev64(vertices, device)
+    f = _faces32(faces, v.device)
+    if w2c is None:
+        c2w = np.asarray(c2w.detach().cpu().numpy() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float64)
+        c2w = c2w.reshape(-1, 4, 4)
+        w2c = np.linalg.inv(c2w) if len(c2w) else c2w
+    m = _dev64(w2c, v.device)
+    m = m.reshape(-1, *m.shape[-2:])
+    return ops.render_depth(v, f, m, H, W, fx, fy, cx, cy, z_near, z_far, small_max_pixels)
+
+
+def _near_plane(vertices):
+    """0.01 x the largest extent of the mesh's axis-aligned box: where open3d's view control is understood to put
+    the near plane of a camera inside the scene (unpinned: open3d is absent)."""
+    if vertices.shape[0] == 0:
+        return 0.01
+    ext = (vertices.max(0).values - vertices.min(0).values).max()
+    return 0.01 * float(ext)
+
+
+def calc_depth_l1(rec_meshfile, gt_meshfile, align=True, n_imgs=1000, seed=0, *, unseen_pc=None, cam_box=None,
+                  H=500, W=500, focal=300., z_near=None, z_far=20., device=None):
+    """eval_recon.py:131-210 (calc_2d_metric) → {"depth_l1_cm", "errors" float64 [n_imgs] (metres), "views" float64
+    [n_imgs,4,4] camera-to-world}, printed as the reference prints it.
+
+    n_imgs views are drawn inside the ground truth's shrunk oriented box (sample_views, `seed`), both meshes are
+    rendered from each (render_depth) and the mean |depth difference| over all pixels (background counts) is
+    averaged.  unseen_pc: the points no view may see, [N,3]; None loads the reference's sidecar
+    gt_meshfile.replace('.ply', '_pc_unseen.npy'); an empty array turns the rejection off.  cam_box = (extents,
+    transform) skips the oriented bounds (no scipy needed).  z_near=None: 0.01 x the largest extent of each
+    mesh's own axis-aligned box.  Deviations from the reference: DESIGN §7b."""
+    if unseen_pc is None:
+        side = gt_meshfile.replace('.ply', '_pc_unseen.npy')
+        try:
+            unseen_pc = np.load(side)
+        except FileNotFoundError:
+            raise FileNotFoundError(f"calc_depth_l1: the unseen-point file {side} is missing; pass unseen_pc= "
+                                    "(an empty [0,3] array turns the view rejection off)") from None
+    unseen_pc = np.asarray(unseen_pc, dtype=np.float64).reshape(-1, 3)
+    rec, gt = load_mesh(rec_meshfile), load_mesh(gt_meshfile)
+    rec_v, gt_v = _dev64(rec["vertices"], device), _dev64(gt["vertices"], device)
+    if not rec_v.is_cuda:
+        raise RuntimeError("calc_depth_l1: nice-slam_amd kernels run on the HIP device only; got a CPU device")
+    rec_f, gt_f = _faces32(rec["faces"], rec_v.device), _faces32(gt["faces"], gt_v.device)
+    if align:
+        rec_v = ops.transform_points(rec_v, icp_align(rec_v, gt_v))
+    extents, transform = cam_box if cam_box is not None else get_cam_position(gt["vertices"])
+    H, W = int(H), int(W)
+    fx = fy = float(focal)
+    cx, cy = H / 2.0 - 0.5, W / 2.0 - 0.5      # as the reference writes them
+    views = sample_views(n_imgs, extents, transform, unseen_pc, seed, H, W, fx, fy, cx, cy, device=gt_v.device)
+    zn_gt = _near_plane(gt_v) if z_near is None else float(z_near)
+    zn_rec = _near_plane(rec_v) if z_near is None else float(z_near)
+    w2c = torch.from_numpy(np.linalg.inv(views)[:, :3, :].copy() if len(views) else np.zeros((0, 3, 4))) \
+        .to(gt_v.device).contiguous()
+    per = max(1, VIEW_BATCH_BYTES // (2 * 4 * H * W))
+    ws = torch.empty(ops.RASTER_WS_BYTES, dtype=torch.uint8, device=gt_v.device)
+    errors = []
+    for v0 in range(0, len(views), per):
+        m = w2c[v0:v0 + per]
+        d_gt = ops.render_depth(gt_v, gt_f, m, H, W, fx, fy, cx, cy, zn_gt, z_far, ws=ws)
+        d_rec = ops.render_depth(rec_v, rec_f, m, H, W, fx, fy, cx, cy, zn_rec, z_far, ws=ws)
+        errors.append(ops.depth_l1(d_gt, d_rec))
+    errors = torch.cat(errors).cpu().numpy() if errors else np.zeros(0)
+    out = {"depth_l1_cm": float(errors.mean() * 100) if len(errors) else float("nan"), "errors": errors,
+           "views": views}
+    print('Depth L1: ', out["depth_l1_cm"])
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1331,3 +1331,96 @@ def kabsch_sums(src, idx, targets):
                                  stream_ptr(dev))
     check(rc, "nslam_kabsch_sums")
     return partials.cpu().numpy().cumsum(0)[-1]  # numpy's cumsum is one sequential chain per column
+
+
+# ------------------------------------------------------------------------------------------------
+# depth L1 (csrc/nslam_raster.hip, csrc/nslam_eval.hip)
+# ------------------------------------------------------------------------------------------------
+RASTER_CLEAR, RASTER_SMALL, RASTER_BIG, RASTER_RESOLVE, RASTER_ALL = 1, 2, 4, 8, 15
+RASTER_SMALL_MAX_PIXELS = 64     # a larger pixel box goes to the list pass (how it was chosen)
+RASTER_WS_BYTES = 64 << 20       # the list's byte budget: 8 M items of 8 bytes
+RASTER_MAX_VIEWS = 65535         # views per launch (one grid row each)
+
+
+def raster_workspace(capacity, device):
+    """A workspace for render_depth whose list of large items holds `capacity` entries (uint8 tensor)."""
+    return torch.empty(lib().nslam_raster_workspace_size(int(capacity)), dtype=torch.uint8, device=device)
+
+
+def render_depth(vertices, faces, w2c, H, W, fx, fy, cx, cy, z_near, z_far, small_max_pixels=None, ws=None,
+                 passes=RASTER_ALL, out=None):
+    """nslam_raster_depth → float32 [B,H,W]: the camera-space z of the nearest triangle along the ray through every
+    pixel centre, 0 where nothing is hit.
+
+    vertices float64 [V,3]; faces int32 [F,3]; w2c float64 [B,3,4] or [B,4,4] (the camera looks along +z, x right,
+    y down).  small_max_pixels: the largest pixel box a (face, view) thread tests itself (None: the default);
+    ws: a raster_workspace (None: one of RASTER_WS_BYTES).  The image does not depend on either.  passes / out:
+    run single passes on an image kept between calls (tools/eval_bench.py's per-stage timing)."""
+    nv, nf = _want_mesh(vertices, faces, "render_depth")
+    dev = vertices.device
+    if not isinstance(w2c, torch.Tensor) or not w2c.is_cuda:
+        raise RuntimeError("w2c: nice-slam_amd kernels run on the HIP device only; got a CPU tensor")
+    if w2c.dim() == 3 and tuple(w2c.shape[1:]) == (4, 4):
+        w2c = w2c[:, :3, :].contiguous()
+    b = int(w2c.shape[0])
+    _want(w2c, "w2c", torch.float64, (b, 3, 4))
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0 or not float(fx) > 0 or not float(fy) > 0:
+        raise ValueError("render_depth: H, W, fx and fy must be positive")
+    if not (0.0 <= float(z_near) < float(z_far)):
+        raise ValueError(f"render_depth: need 0 <= z_near < z_far, got {z_near}, {z_far}")
+    small = RASTER_SMALL_MAX_PIXELS if small_max_pixels is None else int(small_max_pixels)
+    if small < 0:
+        raise ValueError("render_depth: small_max_pixels must not be negative")
+    if out is None:
+        out = torch.empty(b, H, W, dtype=torch.float32, device=dev)
+        if nf == 0:
+            out.zero_()
+    _want(out, "out", torch.float32, (b, H, W))
+    if b == 0 or nf == 0:
+        return out
+    if ws is None:
+        ws = torch.empty(RASTER_WS_BYTES, dtype=torch.uint8, device=dev)
+    _want(ws, "ws", torch.uint8, (None,))
+    for v0 in range(0, b, RASTER_MAX_VIEWS):
+        v1 = min(b, v0 + RASTER_MAX_VIEWS)
+        rc = lib().nslam_raster_depth(ptr(vertices), nv, ptr(faces), nf, ptr(w2c[v0:v1]), v1 - v0, H, W, float(fx),
+                                      float(fy), float(cx), float(cy), float(z_near), float(z_far), small,
+                                      int(passes), ptr(out[v0:v1]), ptr(ws), ws.numel(), stream_ptr(dev))
+        check(rc, "nslam_raster_depth")
+    return out
+
+
+def raster_list_length(ws):
+    """The number of items the last SMALL pass appended to (or, past the capacity, drew instead of) the list."""
+    return int(ws[:8].view(torch.int64)[0])
+
+
+def views_see_any(points, w2c, H, W, fx, fy, cx, cy):
+    """nslam_views_see_any → bool [B]: the view's image holds some point of the cloud (frustum_seen's test).
+
+    points float64 [N,3]; w2c float32 [B,4,4] (inverted on the host by the caller)."""
+    _want(points, "points", torch.float64, (None, 3))
+    b = int(w2c.shape[0])
+    _want(w2c, "w2c", torch.float32, (b, 4, 4))
+    n, dev = points.shape[0], points.device
+    out = torch.zeros(b, dtype=torch.uint8, device=dev)
+    for v0 in range(0, b, RASTER_MAX_VIEWS):
+        v1 = min(b, v0 + RASTER_MAX_VIEWS)
+        rc = lib().nslam_views_see_any(ptr(points), n, ptr(w2c[v0:v1]), v1 - v0, int(H), int(W), float(fx), float(fy),
+                                       float(cx), float(cy), ptr(out[v0:v1]), stream_ptr(dev))
+        check(rc, "nslam_views_see_any")
+    return out.bool()
+
+
+def depth_l1(a, b):
+    """nslam_depth_l1 → float64 [B]: the mean over a view's pixels of |a - b| (float32 [B,H,W] each)."""
+    _want(a, "a", torch.float32, (None, None, None))
+    _want(b, "b", torch.float32, tuple(a.shape))
+    nb, npix = int(a.shape[0]), int(a.shape[1]) * int(a.shape[2])
+    if nb and npix == 0:
+        raise ValueError("depth_l1: the images have no pixels")
+    out = torch.empty(nb, dtype=torch.float64, device=a.device)
+    rc = lib().nslam_depth_l1(ptr(a), ptr(b), nb, npix, ptr(out), stream_ptr(a.device))
+    check(rc, "nslam_depth_l1")
+    return out

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The evaluation kernels at Replica room0 size: ms per stage against the two bars.
 
-    python tools/eval_bench.py [--poses 2000] [--samples 200000] [--repeat 5] [--out profiles/eval_recon.json]
+    python tools/eval_bench.py [--poses 2000] [--samples 200000] [--repeat 5] [--views 1000] [--raster_repeat 3]
+                               [--out profiles/eval_recon.json]
 
 Workload, made procedurally (timing only): the room0 bound as a tessellated box of ~600 k vertices / 1.2 M faces
 with a smooth bump on every wall, 2000 camera poses around the room centre at 680x1200, 200 k surface samples per
@@ -15,6 +16,12 @@ cloud, and 600 k / 1 M vertex clouds for ICP.  Stages, device-event medians of `
                     for the nearest-neighbour stages (wall-clock; skipped when scipy is absent)
   icp_iteration     one ICP iteration at 600 k source / 1 M target vertices (query within 0.1 + Kabsch sums +
                     transform), icp_align the whole loop; kdtree_icp_query the same query on the host
+  depth_l1          the 2D metric's stages on the same mesh: `--views` (1000) views at 500x500 drawn by
+                    sample_views, in batches as calc_depth_l1 makes them; per stage (clear, small pass, big pass,
+                    resolve, L1, view rejection of 2000 candidates against a 100 k-point cloud) the sum over the
+                    batches, median of `--raster_repeat`; the length of the big list; face-views/s and pixels/s;
+                    and the small + big time of one batch for a sweep of small_max_pixels.  The reference's path
+                    needs an OpenGL window: nothing was compared, no bar exists.
 No time or ratio was fixed in advance: the file records what the kernels do against those two bars.  A run without
 a HIP device fails: nothing here is measurable on the CPU.
 """
@@ -98,23 +105,111 @@ def torch_cull(points64, poses, H, W, fx, fy, cx, cy):
         unseen &= ~((0 <= -zz) & (uv[:, 0] < W) & (uv[:, 0] > 0) & (uv[:, 1] < H) & (uv[:, 1] > 0))
     return ~unseen
 
+def event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b), out
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--poses", type=int, default=2000)
-    ap.add_argument("--samples", type=int, default=200000)
-    ap.add_argument("--repeat", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "eval_recon.json"))
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("eval_bench: no HIP device; nothing here can be measured on the CPU")
-    P = importlib.import_module("nice-slam_amd")
+
+def depth_l1_leg(P, verts, faces, bound, n_views, repeat, dev):
+    """The stages of calc_depth_l1 on the procedural mesh → the "depth_l1" entry of the output."""
     E, ops = P.evaluation, P.ops
-    dev = torch.device("cuda:0")
+    H = W = 500
+    fx = fy = 300.0
+    cx = cy = 249.5
+    z_near, z_far = 0.01 * float((bound[:, 1] - bound[:, 0]).max()), 20.0
+    ctr, size = bound.mean(1), bound[:, 1] - bound[:, 0]
+    box = np.eye(4)
+    box[:3, 3] = ctr
+    extents = 0.6 * size
+    # the unseen cloud: a 1.5 m patch half a metre behind the +x wall
+    g = np.random.default_rng(0)
+    pc = np.stack([np.full(100000, bound[0, 1] + 0.5), ctr[1] + 1.5 * (g.random(100000) - 0.5),
+                   ctr[2] + 1.5 * (g.random(100000) - 0.5)], 1)
+    pc_d = torch.from_numpy(pc).to(dev)
+    cand = E.sample_views(2000, extents, box, None, 0)
+    cw = torch.from_numpy(E._check_proj_w2c(cand)).to(dev).contiguous()
+    ms_rej, seen = timed(lambda: ops.views_see_any(pc_d, cw, H, W, fx, fy, cx, cy), repeat)
+    views = E.sample_views(n_views, extents, box, pc, 0, H, W, fx, fy, cx, cy)
+    w2c = torch.from_numpy(np.linalg.inv(views)[:, :3, :].copy()).to(dev).contiguous()
+    rec = (verts + torch.tensor([0.01, -0.005, 0.02], dtype=torch.float64, device=dev)).contiguous()
+    per = max(1, E.VIEW_BATCH_BYTES // (2 * 4 * H * W))
+    ws = torch.empty(ops.RASTER_WS_BYTES, dtype=torch.uint8, device=dev)
+    cap = (ws.numel() - 16) // 8
+    args = (H, W, fx, fy, cx, cy, z_near, z_far)
+    names = (("clear", ops.RASTER_CLEAR), ("small_pass", ops.RASTER_SMALL), ("big_pass", ops.RASTER_BIG),
+             ("resolve", ops.RASTER_RESOLVE))
+
+    def run(small_max, batches):
+        """One pass over `batches` view batches of the ground-truth mesh, stage by stage, then the reconstruction
+        in one call and the L1 → (stage ms summed over the batches, list lengths, per-view errors)."""
+        t = {k: 0.0 for k, _ in names}
+        t["l1"] = 0.0
+        lens, errs = [], []
+        for v0 in batches:
+            m = w2c[v0:v0 + per]
+            d_gt = torch.empty(m.shape[0], H, W, dtype=torch.float32, device=dev)
+            for k, bit in names:
+                ms, _ = event_ms(lambda: ops.render_depth(verts, faces, m, *args, small_max_pixels=small_max, ws=ws,
+                                                          passes=bit, out=d_gt))
+                t[k] += ms
+                if bit == ops.RASTER_SMALL:
+                    lens.append(ops.raster_list_length(ws))
+            d_rec = ops.render_depth(rec, faces, m, *args, small_max_pixels=small_max, ws=ws)
+            ms, e = event_ms(lambda: ops.depth_l1(d_gt, d_rec))
+            t["l1"] += ms
+            errs.append(e)
+        return t, lens, torch.cat(errs)
+
+    starts = list(range(0, n_views, per))
+    run(None, starts[:1])                                         # warm-up
+    sweep = {}
+    for sm in (4, 16, 64, 256, 1024, H * W):
+        t, lens, _ = run(sm, starts[:1])
+        sweep[str(sm)] = {"small_pass_ms": round(t["small_pass"], 3), "big_pass_ms": round(t["big_pass"], 3),
+                          "list_items": lens[0], "list_overflowed": bool(lens[0] > cap)}
+    # the opposite mesh: the room as 12 triangles, every one of which fills a large part of an image — the work
+    # the list pass exists for (a wall of a real ground-truth mesh is a few such triangles)
+    fine = (verts, faces, rec)
+    verts, faces = box_mesh(bound, 2, dev, bump=0.0)
+    rec = verts
+    coarse = {}
+    run(None, starts[:1])
+    for sm in (64, 1024, 16384, H * W):
+        t, lens, _ = run(sm, starts[:1])
+        coarse[str(sm)] = {"small_pass_ms": round(t["small_pass"], 3), "big_pass_ms": round(t["big_pass"], 3),
+                           "list_items": lens[0]}
+    verts, faces, rec = fine
+    runs = [run(None, starts) for _ in range(repeat)]
+    med = {k: round(statistics.median(r[0][k] for r in runs), 3) for k in runs[0][0]}
+    med["view_rejection_2000_candidates"] = round(ms_rej, 4)
+    lens, errs = runs[-1][1], runs[-1][2]
+    raster_ms = med["clear"] + med["small_pass"] + med["big_pass"] + med["resolve"]
+    same = all(torch.equal(r[2], errs) for r in runs)
+    return {"views": n_views, "image": [H, W], "views_per_batch": per, "z_near": z_near, "z_far": z_far,
+            "small_max_pixels": ops.RASTER_SMALL_MAX_PIXELS, "list_capacity": cap,
+            "stages_ms_one_mesh": med, "big_list_items_total": int(sum(lens)),
+            "big_list_items_max_batch": int(max(lens)),
+            "list_overflowed": bool(max(lens) > cap),
+            "face_views_per_s": round(faces.shape[0] * n_views / ((med["small_pass"] + med["big_pass"]) * 1e-3), 1),
+            "pixels_per_s": round(n_views * H * W / (raster_ms * 1e-3), 1),
+            "candidates_rejected_of_2000": int(seen.sum()), "depth_l1_cm": float(errs.mean()) * 100,
+            "errors_equal_across_repeats": bool(same), "small_max_pixels_sweep_one_batch": sweep,
+            "small_max_pixels_sweep_one_batch_12_triangle_room": coarse,
+            "compared_with": "nothing: the reference renders through an open3d OpenGL window; no bar exists",
+            "notes": "all figures measured on this run; device-event times, each stage summed over the view batches "
+                     "of the ground-truth mesh (the reconstruction costs the same again), median of the repeats; "
+                     "the sweep is one batch, run once per value"}
+
+
+def recon_leg(P, a, verts, faces, bound, dev):
+    """cull, sampling, nearest neighbours and ICP → the output's entries for them."""
+    E, ops = P.evaluation, P.ops
     cam = scenes.ROOM0_CAM
-    bound = np.asarray(scenes.ROOM0_BOUND)
     ctr = bound.mean(1)
-    verts, faces = box_mesh(bound, 316, dev)
     big, _ = box_mesh(bound, 408, dev)
     poses = np.stack([scenes.look_pose(ctr, 0.011 * k, 1.1 + 0.4 * np.sin(0.05 * k),
                                        (1.5 * np.sin(0.02 * k), 1.0 * np.cos(0.03 * k), 0.3 * np.sin(0.07 * k)))
@@ -199,6 +294,26 @@ def main():
         out["icp"]["kdtree_query_over_hip_query"] = round(ms_q / st["icp_query"], 1)
     out["notes"] = ("device-event medians after one warm-up; cull_torch, kdtree_* and icp_align are wall-clock, run "
                     "once; procedural room0-sized inputs (timing only); no target was set for these kernels")
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--poses", type=int, default=2000)
+    ap.add_argument("--samples", type=int, default=200000)
+    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--views", type=int, default=1000)
+    ap.add_argument("--raster_repeat", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "eval_recon.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_bench: no HIP device; nothing here can be measured on the CPU")
+    P = importlib.import_module("nice-slam_amd")
+    dev = torch.device("cuda:0")
+    bound = np.asarray(scenes.ROOM0_BOUND)
+    verts, faces = box_mesh(bound, 316, dev)
+    out = recon_leg(P, a, verts, faces, bound, dev)
+    out["depth_l1"] = depth_l1_leg(P, verts, faces, bound, a.views, a.raster_repeat, dev)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
