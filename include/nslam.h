@@ -425,6 +425,22 @@ typedef struct nslam_cam_tail {
 int nslam_cam_grad_step(const nslam_cam_tail* tail, const float* c2w, const double* const* g_pts, int32_t n_parts,
                         const double* z_vals, const float* rays_d, int64_t n_rays, int32_t n_samples, float* g_cam,
                         double* ws, uint32_t* ticket, void* stream);
+/* Additive (ABI stays 24).  nslam_cam_grad_step for the reference's tracking.seperate_LR loop
+ * (Tracker.py:202-247, the TUM-RGBD configs): the quaternion and the translation are two Adam groups there,
+ * both stepped every iteration — elementwise, that is one 7-vector whose elements 0..3 step with lr_quat and
+ * 4..6 with tail.lr, with one step count.  That loop rebuilds camera_tensor = cat([quad, T]) before each
+ * iteration, so the candidate it keeps (Tracker.py:245-247) is the camera BEFORE the iteration's step: with
+ * best_before_step != 0, best receives the camera values read at kernel entry (0: the stepped camera, as
+ * nslam_cam_grad_step).  With lr_quat == tail.lr and best_before_step == 0 the call gives
+ * nslam_cam_grad_step's bits (the same kernel). */
+typedef struct nslam_cam_tail_lr2 {
+  nslam_cam_tail tail;
+  float lr_quat;            /* Adam rate of elements 0..3 (the quaternion) */
+  int32_t best_before_step; /* the best pose is the camera before the step */
+} nslam_cam_tail_lr2;
+int nslam_cam_grad_step_lr2(const nslam_cam_tail_lr2* tail, const float* c2w, const double* const* g_pts,
+                            int32_t n_parts, const double* z_vals, const float* rays_d, int64_t n_rays,
+                            int32_t n_samples, float* g_cam, double* ws, uint32_t* ticket, void* stream);
 
 /* ABI v19: nslam_cam_pose for n cameras in one launch: c2w + k * c2w_stride = get_camera_from_tensor(cams[k]). */
 int nslam_cam_pose_batch(const float* cams, float* c2w, int64_t c2w_stride, int32_t n, void* stream);
@@ -619,6 +635,27 @@ int nslam_raster_depth(const double* verts, int64_t n_verts, const int32_t* face
                        double cy, double z_near, double z_far, int64_t small_max_pixels, int32_t passes,
                        float* depth, void* ws, size_t ws_bytes, void* stream);
 size_t nslam_raster_workspace_size(int64_t capacity);
+
+/* Lens undistortion of a frame's colour image (src/utils/datasets.py:85-88, the TUM-RGBD configs; additive,
+ * csrc/nslam_image.hip): dst = cv2.undistort(src, K, dist) with its defaults — the new camera matrix is K,
+ * bilinear, constant zero border — for an interleaved uint8 image [H][W][C], C in 1..4, and the five
+ * coefficients dist = (k1, k2, p1, p2, k3) (a HOST array).  For the destination pixel (u, v), in float64
+ * without FMA contraction:
+ *   x = (u - cx)/fx;  y = (v - cy)/fy;  r2 = x*x + y*y;  rad = 1 + ((k3*r2 + k2)*r2 + k1)*r2
+ *   xd = x*rad + 2*p1*x*y + p2*(r2 + 2*x*x);   yd = y*rad + p1*(r2 + 2*y*y) + 2*p2*x*y
+ *   X = rint((xd*fx + cx)*32);  Y = rint((yd*fy + cy)*32)     (half to even: 1/32-pixel positions, clamped to
+ *                                                              ±2^30, NaN to -2^30: far outside either way)
+ *   x0 = X >> 5, ax = X & 31, y0 = Y >> 5, ay = Y & 31        (arithmetic shift: floor)
+ *   dst[v][u][c] = ((32-ax)(32-ay) S(x0,y0) + ax(32-ay) S(x0+1,y0) + (32-ax)ay S(x0,y0+1) + ax ay S(x0+1,y0+1)
+ *                   + 512) >> 10,   S(x, y) = src[y][x][c] inside the image, 0 outside
+ * so everything after the one rounding step is exact integer arithmetic (the 10-bit weights equal OpenCV's
+ * 15-bit table for 5-bit fractions); nslam_frustum_rows' 1/32-pixel convention.  A restatement of OpenCV from
+ * its documented behaviour: parity with the library itself is unpinned (absent).  src and dst are device
+ * pointers and may not alias.  One thread per destination pixel, one launch, no host synchronisation.
+ * NSLAM_EINVAL: a null pointer, src == dst, a negative size, C outside 1..4, fx or fy zero or NaN.  An empty
+ * image (H or W zero) is NSLAM_OK without a launch.  NSLAM_EUNSUPPORTED: H*W >= 2^31. */
+int nslam_undistort_u8(const uint8_t* src, int32_t H, int32_t W, int32_t C, double fx, double fy, double cx,
+                       double cy, const double dist[5], uint8_t* dst, void* stream);
 
 enum { NSLAM_WS_SAMPLER = 0 };
 size_t nslam_workspace_size(int which, int64_t n);

@@ -98,6 +98,11 @@ class NslamCamTail(ctypes.Structure):
                 ("best", ctypes.c_void_p)]
 
 
+class NslamCamTailLr2(ctypes.Structure):
+    """nslam_cam_tail_lr2: the tail with the quaternion's own Adam rate and the pre-step best pose."""
+    _fields_ = [("tail", NslamCamTail), ("lr_quat", ctypes.c_float), ("best_before_step", ctypes.c_int32)]
+
+
 class NslamAdamSeg(ctypes.Structure):
     _fields_ = [
         ("param", ctypes.c_void_p),
@@ -140,6 +145,8 @@ EXPORTS = (
     "nslam_transform_points", "nslam_kabsch_sums", "nslam_kabsch_partials",
     # depth L1: mesh rasteriser, view rejection, per-view error (additive: no ABI bump)
     "nslam_raster_depth", "nslam_raster_workspace_size", "nslam_views_see_any", "nslam_depth_l1",
+    # TUM-RGBD: lens undistortion, separate learning rates on the fused camera tail (additive: no ABI bump)
+    "nslam_undistort_u8", "nslam_cam_grad_step_lr2",
 )
 
 _lib = None
@@ -247,6 +254,9 @@ def lib():
         L.nslam_raster_workspace_size.restype = sz
         L.nslam_views_see_any.argtypes = [vp, i64, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp]
         L.nslam_depth_l1.argtypes = [vp, vp, i64, i64, vp, vp]
+        L.nslam_undistort_u8.argtypes = [vp, i32, i32, i32, f64, f64, f64, f64, dp, vp, vp]
+        L.nslam_cam_grad_step_lr2.argtypes = [ctypes.POINTER(NslamCamTailLr2), vp, ctypes.POINTER(vp), i32, vp, vp,
+                                              i64, i32, vp, vp, vp, vp]
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L

@@ -87,6 +87,10 @@ struct CamPartsArgs {
   uint32_t* ticket;
   nslam_cam_tail tail;  // ABI v23 (nslam_cam_grad_step): the camera's Adam step, loss and best pose
   int32_t has_tail;
+  // nslam_cam_grad_step_lr2: the quaternion's own rate (elements 0..3; nslam_cam_grad_step passes tail.lr)
+  // and whether the best pose is the camera as read at kernel entry (the reference's seperate_LR loop)
+  float lr_quat;
+  int32_t best_before;
 };
 
 // ABI v23: what follows a tracking iteration's camera gradient, in the workgroup that formed it (all its
@@ -95,7 +99,8 @@ struct CamPartsArgs {
 // for bit), the step count, and the best-pose update with the stepped camera.  The camera, its Adam state,
 // the step count and the best loss are loaded before the tree (their latency hides behind it); thread 0's
 // epilogue left g_cam in g_lds, published by the tree's barriers.  Every read of *step / *best_loss is
-// issued before those barriers, so thread 0 may replace them after.
+// issued before those barriers, so thread 0 may replace them after.  nslam_cam_grad_step_lr2: elements 0..3
+// step with a.lr_quat, and with a.best_before the best pose receives the camera loaded above, before the step.
 constexpr int kTailSum = 256;
 __device__ void cam_tail(const CamPartsArgs& a, const float* g_lds) {
   const nslam_cam_tail& t = a.tail;
@@ -123,12 +128,13 @@ __device__ void cam_tail(const CamPartsArgs& a, const float* g_lds) {
   if (k >= 7) return;
   const double l = s[0];
   const bool better = t.best_loss && l < bl;  // (NaN: not better, as torch's comparison)
-  const AdamCoef c = adam_coef(t.beta1, t.beta2, t.eps, t.lr, stp);
+  const float p_before = p;
+  const AdamCoef c = adam_coef(t.beta1, t.beta2, t.eps, k < 4 ? a.lr_quat : t.lr, stp);
   adam_one(p, g_lds[k], m, v, c);
   t.cam[k] = p;
   t.exp_avg[k] = m;
   t.exp_avg_sq[k] = v;
-  if (better) t.best[k] = p;
+  if (better) t.best[k] = a.best_before ? p_before : p;
   if (k == 0) {
     *t.step = stp + 1.f;
     *t.loss_out = l;
@@ -281,7 +287,8 @@ unsigned cam_grad_workgroups(int64_t n_rays, int32_t n_samples) {
 
 int cam_grad_parts_launch(const float* cam, const float* c2w, const double* const* g_pts, int32_t n_parts,
                           const double* z_vals, const float* rays_d, int64_t n_rays, int32_t n_samples, float* g_cam,
-                          double* ws, uint32_t* ticket, const nslam_cam_tail* tail, void* stream) {
+                          double* ws, uint32_t* ticket, const nslam_cam_tail* tail, float lr_quat, int32_t best_before,
+                          void* stream) {
   if (!cam || !c2w || !g_cam || !ticket || !ws) return NSLAM_EINVAL;
   if (const int rc = cam_parts_check(g_pts, n_parts, z_vals, rays_d, n_rays, n_samples)) return rc;
   CamPartsArgs a{};
@@ -299,6 +306,8 @@ int cam_grad_parts_launch(const float* cam, const float* c2w, const double* cons
   if (tail) {
     a.tail = *tail;
     a.has_tail = 1;
+    a.lr_quat = lr_quat;
+    a.best_before = best_before;
   }
   hipLaunchKernelGGL(k_cam_grad_parts, dim3(cam_grad_workgroups(n_rays, n_samples)), dim3(kCamThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
@@ -332,16 +341,34 @@ extern "C" int nslam_cam_grad_parts(const float* cam, const float* c2w, const do
                                     const double* z_vals, const float* rays_d, int64_t n_rays, int32_t n_samples,
                                     float* g_cam, double* ws, uint32_t* ticket, void* stream) {
   return cam_grad_parts_launch(cam, c2w, g_pts, n_parts, z_vals, rays_d, n_rays, n_samples, g_cam, ws, ticket, nullptr,
-                               stream);
+                               0.f, 0, stream);
 }
+
+namespace {
+int cam_tail_check(const nslam_cam_tail* tail) {
+  if (!tail || !tail->cam || !tail->exp_avg || !tail->exp_avg_sq || !tail->step || !tail->loss_out) return NSLAM_EINVAL;
+  if (tail->n_rays < 0 || (tail->n_rays > 0 && !tail->ray_loss) || (tail->best_loss && !tail->best)) return NSLAM_EINVAL;
+  return NSLAM_OK;
+}
+}  // namespace
 
 extern "C" int nslam_cam_grad_step(const nslam_cam_tail* tail, const float* c2w, const double* const* g_pts,
                                    int32_t n_parts, const double* z_vals, const float* rays_d, int64_t n_rays,
                                    int32_t n_samples, float* g_cam, double* ws, uint32_t* ticket, void* stream) {
-  if (!tail || !tail->cam || !tail->exp_avg || !tail->exp_avg_sq || !tail->step || !tail->loss_out) return NSLAM_EINVAL;
-  if (tail->n_rays < 0 || (tail->n_rays > 0 && !tail->ray_loss) || (tail->best_loss && !tail->best)) return NSLAM_EINVAL;
+  if (const int rc = cam_tail_check(tail)) return rc;
   return cam_grad_parts_launch(tail->cam, c2w, g_pts, n_parts, z_vals, rays_d, n_rays, n_samples, g_cam, ws, ticket,
-                               tail, stream);
+                               tail, tail->lr, 0, stream);
+}
+
+// The reference's seperate_LR camera loop (Tracker.py:202-247) on the same kernel: two Adam groups over one
+// 7-vector are one elementwise Adam with a per-element rate, and its candidate is the camera before the step.
+extern "C" int nslam_cam_grad_step_lr2(const nslam_cam_tail_lr2* tail, const float* c2w, const double* const* g_pts,
+                                       int32_t n_parts, const double* z_vals, const float* rays_d, int64_t n_rays,
+                                       int32_t n_samples, float* g_cam, double* ws, uint32_t* ticket, void* stream) {
+  if (!tail) return NSLAM_EINVAL;
+  if (const int rc = cam_tail_check(&tail->tail)) return rc;
+  return cam_grad_parts_launch(tail->tail.cam, c2w, g_pts, n_parts, z_vals, rays_d, n_rays, n_samples, g_cam, ws,
+                               ticket, &tail->tail, tail->lr_quat, tail->best_before_step != 0, stream);
 }
 
 extern "C" int nslam_cam_grad_batch(const float* cams, const float* c2w, int64_t c2w_stride, int32_t n_cams,

@@ -1,5 +1,5 @@
-"""Frame sources of the mapping/tracking path: Replica, ScanNet and Azure (Apartment) folders
-(src/utils/datasets.py), plus the checkpoint dict of src/utils/Logger.py.
+"""Frame sources of the mapping/tracking path: Replica, ScanNet, Azure (Apartment) and TUM-RGBD
+folders (src/utils/datasets.py), plus the checkpoint dict of src/utils/Logger.py.
 
 SURVEY.md §8(f) row 4.  Same classes, constructor arguments, sort orders and `__getitem__` contract
 as the reference: `(index, color [H,W,3] float64 in [0,1], depth [H,W] float32 metres × scale,
@@ -16,8 +16,17 @@ f32); the default float64 is the reference's (datasets.py:91).
 frame_reader): worker processes decode ahead into pinned host memory and each frame's H2D copy and
 device-side normalisation run on a side stream, so decode overlaps the consumer's GPU work; it
 yields exactly what `dataset[i]` returns (the same host half and device half).
-Out of scope: CoFusion (OpenEXR), TUM-RGBD, lens undistortion (cv2.undistort) — none is a BASELINE
-config; a config asking for `distortion` raises.
+
+`cam.distortion` (five coefficients k1, k2, p1, p2, k3: the TUM-RGBD configs) undistorts the decoded
+uint8 colour image before /255, never the depth (datasets.py:85-88).  cv2.undistort with its defaults
+(new camera matrix K, bilinear, zero border) is restated as `undistort_u8`: the source position in
+float64, rounded to 1/32 pixel, then exact integer weights (include/nslam.h nslam_undistort_u8) — on
+the device one kernel on the stream `_finish` runs on (ops.undistort_u8, no host synchronisation), on
+"cpu" the numpy twin below, bit for bit the same contract.  The restatement is from OpenCV's documented
+behaviour: parity with OpenCV's own undistortion is unpinned (library absent), like the decoder and
+the resampler above.
+Out of scope: CoFusion (OpenEXR), distortion models other than the five-coefficient one, undistorting
+depth (the reference does not).
 """
 from __future__ import annotations
 
@@ -42,6 +51,45 @@ def _read_depth(path):
         return np.asarray(im)
 
 
+def undistort_u8(src, fx, fy, cx, cy, dist):
+    """cv2.undistort(src, K, dist) with its defaults for a uint8 numpy image [H, W] or [H, W, C] and
+    dist = (k1, k2, p1, p2, k3): the host twin of nslam_undistort_u8 (include/nslam.h has the contract;
+    float64 map, 1/32-pixel positions rounded half to even, 10-bit integer weights, zero border)."""
+    src = np.asarray(src)
+    if src.dtype != np.uint8 or src.ndim not in (2, 3):
+        raise ValueError("undistort_u8: src must be a uint8 [H, W] or [H, W, C] image")
+    k1, k2, p1, p2, k3 = _five(dist)
+    H, W = src.shape[:2]
+    img = src.reshape(H, W, -1).astype(np.int64)
+    v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    x, y = (u - cx) / fx, (v - cy) / fy
+    r2 = x * x + y * y
+    rad = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2
+    xd = x * rad + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+    yd = y * rad + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+
+    def fixed5(t):  # (NaN and anything beyond ±2^30: far outside the image either way)
+        return np.rint(np.clip(np.nan_to_num(t, nan=-2.0 ** 30), -2.0 ** 30, 2.0 ** 30)).astype(np.int64)
+
+    X, Y = fixed5((xd * fx + cx) * 32.0), fixed5((yd * fy + cy) * 32.0)
+    x0, y0, ax, ay = X >> 5, Y >> 5, (X & 31)[..., None], (Y & 31)[..., None]
+
+    def tap(xx, yy):
+        ok = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
+        return np.where(ok[..., None], img[np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)], 0)
+
+    out = ((32 - ax) * (32 - ay) * tap(x0, y0) + ax * (32 - ay) * tap(x0 + 1, y0)
+           + (32 - ax) * ay * tap(x0, y0 + 1) + ax * ay * tap(x0 + 1, y0 + 1) + 512) >> 10
+    return out.astype(np.uint8).reshape(src.shape)
+
+
+def _five(dist):
+    dist = [float(v) for v in np.asarray(dist, dtype=np.float64).reshape(-1)]
+    if len(dist) != 5:
+        raise ValueError(f"cam.distortion must be the five coefficients (k1, k2, p1, p2, k3), got {len(dist)}")
+    return dist
+
+
 def _flip_yz(c2w):
     """datasets.py:134-135 (and :170-171, :205-206): camera y and z axes negated."""
     c2w = np.array(c2w, dtype=np.float64).reshape(4, 4)
@@ -62,8 +110,7 @@ class BaseDataset(torch.utils.data.Dataset):
         cam = cfg["cam"]
         self.png_depth_scale = cam["png_depth_scale"]
         self.H, self.W, self.fx, self.fy, self.cx, self.cy = cam["H"], cam["W"], cam["fx"], cam["fy"], cam["cx"], cam["cy"]
-        if "distortion" in cam:
-            raise NotImplementedError("lens undistortion (cv2.undistort) is out of scope")
+        self.distortion = _five(cam["distortion"]) if "distortion" in cam else None
         self.crop_size = cam.get("crop_size")
         folder = getattr(args, "input_folder", None) if args is not None else None
         self.input_folder = cfg["data"]["input_folder"] if folder is None else folder
@@ -95,6 +142,12 @@ class BaseDataset(torch.utils.data.Dataset):
         # which is not the reference's correctly-rounded quotient.  Depth is divided on the host
         # (float32, :92) for the same reason.  Resize and crops then run on the device.
         u8 = u8.to(self.device, non_blocking=non_blocking)
+        if self.distortion is not None:  # datasets.py:85-88: the colour image only, before /255
+            if u8.is_cuda:  # (this stream: the side stream under prefetch)
+                from .ops import undistort_u8 as undistort_dev
+                u8 = undistort_dev(u8.contiguous(), self.fx, self.fy, self.cx, self.cy, self.distortion)
+            else:
+                u8 = torch.from_numpy(undistort_u8(u8.numpy(), self.fx, self.fy, self.cx, self.cy, self.distortion))
         color = self._lut(u8.device)[u8.long()]
         depth = depth.to(self.device, non_blocking=non_blocking)
         H, W = depth.shape
@@ -228,7 +281,81 @@ class ScanNet(BaseDataset):
             self.poses.append(_flip_yz(rows))
 
 
-dataset_dict = {"replica": Replica, "scannet": ScanNet, "azure": Azure}
+class TUM_RGBD(BaseDataset):
+    """datasets.py:234-321: rgb.txt / depth.txt / groundtruth.txt (else pose.txt) associated by time
+    stamp, thinned to 32 frames per second, poses relative to the first kept frame."""
+
+    def __init__(self, cfg, args, scale, device="cuda:0", **kw):
+        super().__init__(cfg, args, scale, device, **kw)
+        self.color_paths, self.depth_paths, self.poses = self.loadtum(self.input_folder, frame_rate=32)
+        self.n_img = len(self.color_paths)
+
+    @staticmethod
+    def parse_list(path, skiprows=0):
+        """np.loadtxt(path, delimiter=' ', dtype=str, skiprows=skiprows) (datasets.py:242-246): the first
+        `skiprows` lines dropped whatever they hold, '#' starts a comment, fields split at single spaces."""
+        with open(path) as f:
+            lines = f.read().splitlines()[skiprows:]
+        rows = [t.split(" ") for t in (line.split("#", 1)[0].strip() for line in lines) if t]
+        return np.array(rows, dtype=np.str_)
+
+    @staticmethod
+    def associate_frames(t_image, t_depth, t_pose, max_dt=0.08):
+        """datasets.py:248-265: per colour stamp the nearest depth and pose stamps (first index on a tie),
+        kept when both gaps are < max_dt."""
+        out = []
+        for i, t in enumerate(t_image):
+            j = int(np.argmin(np.abs(t_depth - t)))
+            k = int(np.argmin(np.abs(t_pose - t)))
+            if np.abs(t_depth[j] - t) < max_dt and np.abs(t_pose[k] - t) < max_dt:
+                out.append((i, j, k))
+        return out
+
+    @staticmethod
+    def pose_matrix_from_quaternion(pvec):
+        """tx ty tz qx qy qz qw → 4×4 (datasets.py:314-321, scipy's Rotation.from_quat(...).as_matrix():
+        the quaternion normalised, then the matrix from its squares and products), float64 numpy."""
+        x, y, z, w = np.asarray(pvec[3:], dtype=np.float64) / np.linalg.norm(np.asarray(pvec[3:], dtype=np.float64))
+        x2, y2, z2, w2 = x * x, y * y, z * z, w * w
+        xy, zw, xz, yw, yz, xw = x * y, z * w, x * z, y * w, y * z, x * w
+        pose = np.eye(4)
+        pose[:3, :3] = [[x2 - y2 - z2 + w2, 2 * (xy - zw), 2 * (xz + yw)],
+                        [2 * (xy + zw), -x2 + y2 - z2 + w2, 2 * (yz - xw)],
+                        [2 * (xz - yw), 2 * (yz + xw), -x2 - y2 + z2 + w2]]
+        pose[:3, 3] = pvec[:3]
+        return pose
+
+    def loadtum(self, datapath, frame_rate=-1):
+        """datasets.py:267-312."""
+        pose_list = os.path.join(datapath, "groundtruth.txt")
+        if not os.path.isfile(pose_list):
+            pose_list = os.path.join(datapath, "pose.txt")
+        image_data = self.parse_list(os.path.join(datapath, "rgb.txt"))
+        depth_data = self.parse_list(os.path.join(datapath, "depth.txt"))
+        pose_data = self.parse_list(pose_list, skiprows=1)
+        pose_vecs = pose_data[:, 1:].astype(np.float64)
+        t_image = image_data[:, 0].astype(np.float64)
+        assoc = self.associate_frames(t_image, depth_data[:, 0].astype(np.float64), pose_data[:, 0].astype(np.float64))
+        keep = [0]
+        for i in range(1, len(assoc)):
+            if t_image[assoc[i][0]] - t_image[assoc[keep[-1]][0]] > 1.0 / frame_rate:
+                keep.append(i)
+        images, depths, poses, inv_pose = [], [], [], None
+        for ix in keep:
+            i, j, k = assoc[ix]
+            images.append(os.path.join(datapath, str(image_data[i, 1])))
+            depths.append(os.path.join(datapath, str(depth_data[j, 1])))
+            c2w = self.pose_matrix_from_quaternion(pose_vecs[k])
+            if inv_pose is None:  # every pose relative to the first kept one, which is exactly eye(4)
+                inv_pose = np.linalg.inv(c2w)
+                c2w = np.eye(4)
+            else:
+                c2w = inv_pose @ c2w
+            poses.append(_flip_yz(c2w))
+        return images, depths, poses
+
+
+dataset_dict = {"replica": Replica, "scannet": ScanNet, "azure": Azure, "tumrgbd": TUM_RGBD}
 
 
 def get_dataset(cfg, args, scale, device="cuda:0", **kw):

@@ -774,14 +774,25 @@ class TrackingEngine:
         return (len(ps) == 1 and ps[0] is cam and optimizer.param_groups[0].get("rows") is None
                 and cam not in optimizer.mirrors and cam.is_contiguous() and cam.numel() == 7)
 
-    def iteration(self, cam, depth, color, pix, optimizer, n=None, seed=0, best=None):
+    def iteration(self, cam, depth, color, pix, optimizer, n=None, seed=0, best=None, lr_quat=None,
+                  best_before_step=False):
         """One camera iteration on frame (depth [H,W], color [H,W,3]) with pixel draws `pix`
         (int64 [n], select_uv indices into the edge-cropped window), or pix=None: n pixels drawn inside
         the gather kernel (uniform over the window, stream `seed`; capturable in a hipGraph).  cam: [7]
         leaf tensor whose .grad the optimizer reads.  Returns the loss (device f64 scalar) of the pose
         BEFORE the step: the kept rays' losses summed in a fixed order (nslam_loss_sum_best; a buffer the
         next call overwrites), which with best = (best_loss, best_cam) also keeps the best pose
-        (Tracker.py:245-247) in the same launch."""
+        (Tracker.py:245-247) in the same launch.
+        lr_quat / best_before_step: the reference's seperate_LR loop (Tracker.py:202-247) — the quaternion
+        (elements 0..3) steps with lr_quat, the translation with the optimizer's lr, and the best pose kept is
+        the camera BEFORE the step (that loop rebuilds camera_tensor from its two leaves before each
+        iteration).  Both live in the fused camera tail (nslam_cam_grad_step_lr2) only: with cam_tail or
+        cam_parts off, or an optimizer the tail does not apply to, the call raises, it does not step with one
+        rate."""
+        lr2 = lr_quat is not None or best_before_step
+        if lr2 and not (self.cam_parts and self.cam_tail and self._tail_ok(optimizer, cam)):
+            raise RuntimeError("TrackingEngine.iteration: lr_quat / best_before_step need the fused camera tail "
+                               "(cam_parts and cam_tail on, a FusedAdam over the camera 7-vector alone)")
         fx, fy, cx, cy = self.intr
         n = pix.numel() if pix is not None else int(n)
         draw = self.eng.draws(seed) if pix is None else None
@@ -810,7 +821,8 @@ class TrackingEngine:
                 adam = (ex, ex2, stp, optimizer.group_of(cam)["lr"], *optimizer.betas, optimizer.eps)
                 bl, bc = (None, None) if best is None else (best[0], best[1])
                 ops.cam_grad_step(cam.detach(), c2w, gps, z, rd, cam.grad, self._cam_ws, self._cam_ticket, adam,
-                                  ray_loss, self._loss, bl, bc)
+                                  ray_loss, self._loss, bl, bc, lr_quat=lr_quat,
+                                  best_before_step=best_before_step)
                 return self._loss
             ops.cam_grad_parts(cam.detach(), c2w, gps, z, rd, cam.grad, self._cam_ws, self._cam_ticket)
         else:

@@ -711,11 +711,14 @@ def cam_grad_parts(cam, c2w, g_pts, z, rd, out, ws, ticket):
     return out
 
 
-def cam_grad_step(cam, c2w, g_pts, z, rd, g_cam, ws, ticket, adam, ray_loss, loss_out, best_loss=None, best=None):
+def cam_grad_step(cam, c2w, g_pts, z, rd, g_cam, ws, ticket, adam, ray_loss, loss_out, best_loss=None, best=None,
+                  lr_quat=None, best_before_step=False):
     """nslam_cam_grad_step (ABI v23): cam_grad_parts, then in its last workgroup the camera's Adam step in
     place (adam = (exp_avg [7], exp_avg_sq [7], step [1], lr, beta1, beta2, eps)), loss_out = the fixed-order
     sum of ray_loss and, with best_loss / best, the best-pose update — bit-identical to cam_grad_parts +
-    FusedAdam.step + loss_sum_best, in one launch."""
+    FusedAdam.step + loss_sum_best, in one launch.
+    lr_quat (a rate for elements 0..3) or best_before_step (best = the camera before the step) select
+    nslam_cam_grad_step_lr2, the reference's seperate_LR loop (Tracker.py:202-247) on the same kernel."""
     n, S = z.shape
     ex, ex2, stp, lr, b1, b2, eps = adam
     checks = [(cam, torch.float32, (7,)), (c2w, torch.float32, (3, 4)), (z, torch.float64, (n, S)),
@@ -729,11 +732,41 @@ def cam_grad_step(cam, c2w, g_pts, z, rd, g_cam, ws, ticket, adam, ray_loss, los
     tail = _lib.NslamCamTail(ptr(cam), ptr(ex), ptr(ex2), ptr(stp), float(lr), float(b1), float(b2), float(eps),
                              ptr(ray_loss), ray_loss.numel(), ptr(loss_out), ptr(best_loss), ptr(best))
     bufs = (ctypes.c_void_p * len(g_pts))(*[ptr(g) for g in g_pts])
+    fn, name = lib().nslam_cam_grad_step, "nslam_cam_grad_step"
+    if lr_quat is not None or best_before_step:
+        tail = _lib.NslamCamTailLr2(tail, float(lr if lr_quat is None else lr_quat), int(bool(best_before_step)))
+        fn, name = lib().nslam_cam_grad_step_lr2, "nslam_cam_grad_step_lr2"
     with _span("cam_grad"):
-        rc = lib().nslam_cam_grad_step(ctypes.byref(tail), ptr(c2w), bufs, len(g_pts), ptr(z), ptr(rd), n, S,
-                                       ptr(g_cam), ptr(ws), ptr(ticket), stream_ptr(cam.device))
-    check(rc, "nslam_cam_grad_step")
+        rc = fn(ctypes.byref(tail), ptr(c2w), bufs, len(g_pts), ptr(z), ptr(rd), n, S, ptr(g_cam), ptr(ws),
+                ptr(ticket), stream_ptr(cam.device))
+    check(rc, name)
     return loss_out
+
+
+def undistort_u8(src, fx, fy, cx, cy, dist, out=None):
+    """nslam_undistort_u8: cv2.undistort(src, K, dist) with its defaults (new camera matrix K, bilinear,
+    zero border; 1/32-pixel positions, integer weights — include/nslam.h) for a contiguous uint8 device image
+    [H, W, C] or [H, W], C in 1..4, and dist = (k1, k2, p1, p2, k3).  One launch on the current stream, no
+    host synchronisation.  Returns a new image (or `out`, which may not be src)."""
+    if src.dtype != torch.uint8 or src.dim() not in (2, 3) or not src.is_contiguous():
+        raise ValueError("undistort_u8: src must be a contiguous uint8 [H, W] or [H, W, C]")
+    C = 1 if src.dim() == 2 else src.shape[2]
+    dist = [float(v) for v in dist]
+    if len(dist) != 5:
+        raise ValueError(f"undistort_u8: dist must be (k1, k2, p1, p2, k3), got {len(dist)} coefficients")
+    if not 1 <= C <= 4:
+        raise ValueError(f"undistort_u8: 1..4 channels, got {C}")
+    if out is None:
+        out = torch.empty_like(src)
+    _expect("undistort_u8", [(out, torch.uint8, src.shape)])
+    if out.data_ptr() == src.data_ptr() and src.numel():
+        raise ValueError("undistort_u8: out may not alias src")
+    if src.numel() == 0:
+        return out
+    rc = lib().nslam_undistort_u8(ptr(src), src.shape[0], src.shape[1], C, float(fx), float(fy), float(cx), float(cy),
+                                  (ctypes.c_double * 5)(*dist), ptr(out), stream_ptr(src.device))
+    check(rc, "nslam_undistort_u8")
+    return out
 
 
 def cam_vector_batch(c2w, out, copy=None):

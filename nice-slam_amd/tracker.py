@@ -3,6 +3,13 @@
 `optimize_cam_in_batch` keeps the reference's signature and semantics (Tracker.py:71-128).
 The frame loop's per-frame logic (Tracker.py:184-256) is `track_frame`; dataset loading,
 process synchronisation and visualisation (Tracker.py:144-183) are out of scope.
+
+tracking.seperate_LR (the TUM-RGBD configs; Tracker.py:202-209) takes the same fused paths as a single rate:
+the reference's two Adam groups (translation lr, quaternion lr·0.2) are one elementwise Adam over the 7-vector
+with a per-element rate, and its candidate is the camera before the iteration's step (it rebuilds
+camera_tensor from the two leaves at the top of every iteration, Tracker.py:226-227) — both are arguments of
+the fused camera tail (nslam_cam_grad_step_lr2).  So a fused seperate_LR tracker without a generator draws
+its pixels in the gather kernel, as every other fused tracker does; `fused = False` keeps the autograd loop.
 """
 from __future__ import annotations
 
@@ -145,8 +152,7 @@ class Tracker(object):
         gt_depth, gt_color = gt_depth.to(device), gt_color.to(device)
         if idx == 0 or self.gt_camera:
             return gt_c2w.clone()
-        if (self.fused and self.graphs and not self.seperate_LR and self.generator is None
-                and _common.select_uv is _SELECT_UV):
+        if self.fused and self.graphs and self.generator is None and _common.select_uv is _SELECT_UV:
             return self._track_graph(gt_color, gt_depth, pre_c2w,
                                      prev2_c2w if self.const_speed_assumption else None)
         if self.const_speed_assumption and prev2_c2w is not None:
@@ -158,6 +164,8 @@ class Tracker(object):
         # (on the device: no host round trip per frame)
         camera_tensor = camera_tensors(est.detach().float()[None])[0] if self.fused else \
             get_tensor_from_camera(est.detach()).to(device)
+        if self.fused:  # (seperate_LR too: two rates on the fused camera tail)
+            return self._track_fused(camera_tensor, gt_color, gt_depth)
         if self.seperate_LR:
             T = camera_tensor[-3:].clone().requires_grad_(True)
             quad = camera_tensor[:4].clone().requires_grad_(True)
@@ -167,8 +175,6 @@ class Tracker(object):
             camera_tensor = camera_tensor.clone().requires_grad_(True)
             optimizer = torch.optim.Adam([camera_tensor], lr=self.cam_lr)
         best, best_loss = None, np.inf
-        if self.fused and not self.seperate_LR:
-            return self._track_fused(camera_tensor, gt_color, gt_depth)
         for _ in range(self.num_cam_iters):
             if self.seperate_LR:
                 camera_tensor = torch.cat([quad, T], 0)
@@ -178,10 +184,16 @@ class Tracker(object):
         bottom = torch.tensor([[0, 0, 0, 1.0]], dtype=torch.float32, device=device)
         return torch.cat([get_camera_from_tensor(best), bottom], 0)
 
+    def _lr2(self):
+        """iteration()'s keywords for tracking.seperate_LR (Tracker.py:202-209, 226-227): the quaternion's
+        Adam group steps with lr·0.2, and the candidate kept is the camera before the step."""
+        return {"lr_quat": self.cam_lr * 0.2, "best_before_step": True} if self.seperate_LR else {}
+
     def _track_fused(self, camera_tensor, gt_color, gt_depth):
         """The camera loop of track_frame (Tracker.py:225-250) on the TrackingEngine: the best pose
-        (lowest pre-step loss → the pose right after that step, as the reference keeps it) is
-        selected on the device; no host sync.  Without a generator the pixels are drawn in the gather
+        (lowest pre-step loss → the pose right after that step, as the reference keeps it; with
+        seperate_LR the pose before it, as the reference keeps it there) is selected on the device; no
+        host sync.  Without a generator the pixels are drawn in the gather
         kernel and the whole loop is ONE hipGraph, captured on the first frame and replayed on every
         later one (the frame is copied into persistent slots; a fresh Adam per frame by resetting its
         state).  With a generator (pinned draws): torch.randint per iteration, eager."""
@@ -196,7 +208,7 @@ class Tracker(object):
         color = gt_color.float().contiguous()
         for _ in range(self.num_cam_iters):
             pix = torch.randint(eng.n_window(), (self.tracking_pixels,), device=device, generator=self.generator)
-            eng.iteration(cam, depth, color, pix, opt, best=(best_loss, best))  # (+ Tracker.py:245-247)
+            eng.iteration(cam, depth, color, pix, opt, best=(best_loss, best), **self._lr2())  # (+ Tracker.py:245-247)
         bottom = torch.tensor([[0, 0, 0, 1.0]], dtype=torch.float32, device=device)
         return torch.cat([get_camera_from_tensor(best), bottom], 0)
 
@@ -229,6 +241,7 @@ class Tracker(object):
         if speed:
             st["prev2"][:3].copy_(prev2_c2w[:3])
         n, iters = self.tracking_pixels, self.num_cam_iters
+        lr2 = self._lr2()
 
         def frame(zero_lr=False):
             pre = st["pre"]
@@ -240,12 +253,13 @@ class Tracker(object):
             for _ in range(1 if zero_lr else iters):
                 # (the iteration's loss launch also keeps the best pose, Tracker.py:245-247)
                 eng.iteration(cam, st["depth"], st["color"], None, opt, n=n, seed=self._draw_seed,
-                              best=(best_loss, best))
+                              best=(best_loss, best), **(dict(lr2, lr_quat=0.0) if zero_lr and lr2 else lr2))
             ops.cam_pose(best, st["out"][:3])  # get_camera_from_tensor(best), one launch
 
-        key = (iters, n, speed)
+        key = (iters, n, speed, self.seperate_LR)
         if key not in self._graphs:
-            # one zero-lr eager iteration (camera grad, Adam ticket, draw counter, caches made before capture);
+            # one zero-lr eager iteration (both rates zero with seperate_LR; camera grad, Adam ticket, draw
+            # counter, caches made before capture);
             # the draw stream is rewound, so the frame draws as it would have eagerly
             ctr = eng.eng.draws(self._draw_seed).counter
             ctr0 = ctr.clone()
