@@ -657,6 +657,90 @@ size_t nslam_raster_workspace_size(int64_t capacity);
 int nslam_undistort_u8(const uint8_t* src, int32_t H, int32_t W, int32_t C, double fx, double fy, double cx,
                        double cy, const double dist[5], uint8_t* dst, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * iMAP* (configs/imap.yaml, run.py --imap; additive, no ABI bump): the 256-wide Fourier MLP
+ * (csrc/nslam_imap.hip), volume-density compositing (csrc/nslam_composite.hip) and the hierarchical sampler
+ * (csrc/nslam_sampler.hip).
+ *
+ * The model is config.get_model(cfg, nice=False) (src/conv_onet/config.py; decoder.py:91-203 with c_dim=0):
+ *   e = sin(p.float() @ B)            B [3][93]
+ *   h1 = relu(W0 e + b0)              W0 [256][93]
+ *   h(i+1) = relu(Wi hi + bi)         Wi [256][256], i = 1..3
+ *   raw = Wo h4 + bo                  Wo [4][256]     (no activation; rgb is not squashed)
+ * All arithmetic is float32 (v_mfma_f32_32x32x2_f32 for the four hidden layers); sin / cos are the accurate
+ * ones of the Fourier features of the NICE decoders. */
+typedef struct nslam_imap_params { /* the module's tensors in their natural (state_dict) layout */
+  const float* B;    /* embedder._B            [3][93]                */
+  const float* w[4]; /* pts_linears.i.weight   [256][93], [256][256]x3 */
+  const float* b[4]; /* pts_linears.i.bias     [256]                  */
+  const float* wo;   /* output_linear.weight   [4][256]               */
+  const float* bo;   /* output_linear.bias     [4]                    */
+} nslam_imap_params;
+
+typedef struct nslam_imap_grads { /* caller-owned, same layouts; the backward ADDS into them */
+  float* B;
+  float* w[4];
+  float* b[4];
+  float* wo;
+  float* bo;
+} nslam_imap_grads;
+
+typedef struct nslam_imap_query { /* the points, as the fused NICE query takes them */
+  const double* pts;    /* [n][3] float64, or NULL for the ray form                               */
+  const float* rays_o;  /* ray form: p = rays_o[r] + rays_d[r] * z_vals[i] in float64, r = i / n_samples */
+  const float* rays_d;
+  const double* z_vals; /* [n]                                                                    */
+  int64_t n_samples;
+  double bound_lo[3];   /* Renderer.eval_points' rule (Renderer.py:43-57): a point that is not strictly */
+  double bound_hi[3];   /* inside gets raw[3] = 100 (rgb kept); -inf / +inf switch the test off   */
+} nslam_imap_query;
+
+/* The hidden layers read their weights as MFMA fragments: nslam_imap_pack writes them (forward and
+ * transposed, zero-padded from 93 to 96) into `packed` (nslam_imap_packed_size() bytes) from `params`.
+ * Call it again whenever the parameters changed. */
+size_t nslam_imap_packed_size(void);
+int nslam_imap_pack(const nslam_imap_params* params, float* packed, void* stream);
+
+/* raw [n][4] float32.  tape (NULL = none; nslam_imap_tape_size(n) bytes) receives the post-ReLU activations
+ * h1..h4 of every 128-point tile, which the backward reads (its ReLU masks are h > 0; the embedding is
+ * recomputed from the points).  n < 2^31. */
+size_t nslam_imap_tape_size(int64_t n);
+int nslam_imap_fwd(const nslam_imap_params* params, const float* packed, const nslam_imap_query* q, int64_t n,
+                   float* raw, void* tape, void* stream);
+
+/* Backward of nslam_imap_fwd for the cotangent g_raw [n][4]: parameter gradients ADDED into `grads` (NULL =
+ * none) and, when g_pts is not NULL, d/dp [n][3] float64 (dp = B (de * cos(pB))) WRITTEN to it.  An
+ * out-of-bound point passes nothing through its density (the reference overwrites it in place).
+ * Three launches plus a reduction: the cotangent chain da(i-1) = Wi^T (da_i * mask_i) per 128-point tile,
+ * split-K weight gradients dW_i = sum_p da_i^T h(i-1) per slab of tiles, and a sum of the slabs' partials in a
+ * fixed order — no atomics, so two calls with the same inputs give the same bits. */
+size_t nslam_imap_bwd_workspace_size(int64_t n);
+int nslam_imap_bwd(const nslam_imap_params* params, const float* packed, const nslam_imap_query* q, int64_t n,
+                   const float* g_raw, const void* tape, const nslam_imap_grads* grads, double* g_pts, void* ws,
+                   size_t ws_bytes, void* stream);
+
+/* raw2outputs_nerf_color(occupancy=False) (src/common.py:222-245) and its backward:
+ *   dists_k = float(z_(k+1) - z_k), the last one 1e10;  dists *= |rays_d|  (float32)
+ *   alpha_k = 1 - exp(-relu(raw_k[3]) dists_k);  T_k = prod_(j<k) (1 - alpha_j + 1e-10);  w_k = alpha_k T_k
+ *   rgb = sum w_k raw_k[:3] (f32);  depth = sum w_k z_k (f64);  var = sum w_k (z_k - depth)^2 (f64)
+ * weights [n][S] float32 (may be NULL) is what the importance sampler reads.  The backward writes g_raw
+ * [n][S][4] and, when not NULL, g_rays_d [n][3] (the norm factor's edge).  S <= 256. */
+int nslam_composite_density_fwd(const float* raw, const double* z_vals, const float* rays_d, int64_t n_rays,
+                                int32_t n_samples, double* depth, double* var, float* color, float* weights,
+                                void* stream);
+int nslam_composite_density_bwd(const float* raw, const double* z_vals, const float* rays_d, int64_t n_rays,
+                                int32_t n_samples, const double* g_depth, const double* g_var,
+                                const float* g_color, float* g_raw, float* g_rays_d, void* stream);
+
+/* sample_pdf(z_mid, weights[..., 1:-1], N, det=True) (src/common.py:19-63) merged with the coarse samples
+ * (sort(cat(z_vals, z_samples)), Renderer.py:182-186): z_out [n][S + N] float64; z_samples [n][N] receives the
+ * new samples alone (either may be NULL).  u [N] float32 is the
+ * deterministic torch.linspace(0, 1, N).  Per ray: pdf = (w + 1e-5) / sum, a sequential float32 cdf, the
+ * right-sided search, denom < 1e-5 -> 1, samples in float64.  3 <= S <= 256, 1 <= N <= 128. */
+int nslam_sample_importance(const double* z_vals, const float* weights, const float* u, int64_t n_rays,
+                            int32_t n_samples, int32_t n_importance, double* z_out, double* z_samples,
+                            void* stream);
+
 enum { NSLAM_WS_SAMPLER = 0 };
 size_t nslam_workspace_size(int which, int64_t n);
 

@@ -122,6 +122,18 @@ class NslamAdamSeg(ctypes.Structure):
     ]
 
 
+class NslamImapParams(ctypes.Structure):
+    """nslam_imap_params / nslam_imap_grads: the iMAP* module's tensors in state_dict layout."""
+    _fields_ = [("B", ctypes.c_void_p), ("w", ctypes.c_void_p * 4), ("b", ctypes.c_void_p * 4),
+                ("wo", ctypes.c_void_p), ("bo", ctypes.c_void_p)]
+
+
+class NslamImapQuery(ctypes.Structure):
+    _fields_ = [("pts", ctypes.c_void_p), ("rays_o", ctypes.c_void_p), ("rays_d", ctypes.c_void_p),
+                ("z_vals", ctypes.c_void_p), ("n_samples", ctypes.c_int64), ("bound_lo", ctypes.c_double * 3),
+                ("bound_hi", ctypes.c_double * 3)]
+
+
 # every symbol include/nslam.h declares (tests check that the library exports all of them)
 EXPORTS = (
     "nslam_pack_layout", "nslam_sample_rays", "nslam_query_fwd", "nslam_query_bwd", "nslam_query_bwd_workspace_size",
@@ -147,6 +159,10 @@ EXPORTS = (
     "nslam_raster_depth", "nslam_raster_workspace_size", "nslam_views_see_any", "nslam_depth_l1",
     # TUM-RGBD: lens undistortion, separate learning rates on the fused camera tail (additive: no ABI bump)
     "nslam_undistort_u8", "nslam_cam_grad_step_lr2",
+    # iMAP*: the 256-wide Fourier MLP, density compositing, the hierarchical sampler (additive: no ABI bump)
+    "nslam_imap_packed_size", "nslam_imap_pack", "nslam_imap_tape_size", "nslam_imap_fwd",
+    "nslam_imap_bwd_workspace_size", "nslam_imap_bwd", "nslam_composite_density_fwd",
+    "nslam_composite_density_bwd", "nslam_sample_importance",
 )
 
 _lib = None
@@ -257,6 +273,19 @@ def lib():
         L.nslam_undistort_u8.argtypes = [vp, i32, i32, i32, f64, f64, f64, f64, dp, vp, vp]
         L.nslam_cam_grad_step_lr2.argtypes = [ctypes.POINTER(NslamCamTailLr2), vp, ctypes.POINTER(vp), i32, vp, vp,
                                               i64, i32, vp, vp, vp, vp]
+        ipp, iqp = ctypes.POINTER(NslamImapParams), ctypes.POINTER(NslamImapQuery)
+        L.nslam_imap_packed_size.argtypes = []
+        L.nslam_imap_packed_size.restype = sz
+        L.nslam_imap_pack.argtypes = [ipp, vp, vp]
+        L.nslam_imap_tape_size.argtypes = [i64]
+        L.nslam_imap_tape_size.restype = sz
+        L.nslam_imap_fwd.argtypes = [ipp, vp, iqp, i64, vp, vp, vp]
+        L.nslam_imap_bwd_workspace_size.argtypes = [i64]
+        L.nslam_imap_bwd_workspace_size.restype = sz
+        L.nslam_imap_bwd.argtypes = [ipp, vp, iqp, i64, vp, vp, ipp, vp, vp, sz, vp]
+        L.nslam_composite_density_fwd.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
+        L.nslam_composite_density_bwd.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
+        L.nslam_sample_importance.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L

@@ -151,14 +151,31 @@ def camera_tensors(RT):
     return torch.cat([q, T], -1).float()
 
 
-def raw2outputs_nerf_color(raw, z_vals, rays_d, occupancy=False, device="cuda:0"):
-    """src/common.py:204-245 → (depth, var, rgb, weights); occupancy mode on the HIP kernel.
+def sample_pdf(bins, weights, N_samples, det=False, device="cuda:0", z_vals=None):
+    """src/common.py:19-63 (hierarchical sampling) with det=True, on the HIP kernel.
 
-    `weights` is recomputed by the kernel's backward and not materialised; it is returned as None
-    (no caller on the NICE-SLAM path uses it: N_importance = 0).
+    The kernel works on the coarse samples themselves (it fuses the sort that follows at the one call site,
+    Renderer.py:182-186; ops.sample_importance), so they are passed as the keyword z_vals (an extension): bins
+    are their midpoints and weights the composited weights[..., 1:-1].  Returns the N_samples new samples."""
+    if not det:
+        raise NotImplementedError("sample_pdf with random u (perturb > 0): no configuration sets it")
+    if z_vals is None:
+        raise NotImplementedError("sample_pdf takes the coarse samples as z_vals= (bins are their midpoints)")
+    if bins.shape[-1] != z_vals.shape[-1] - 1 or weights.shape[-1] != z_vals.shape[-1] - 2:
+        raise ValueError("bins / weights must be z_vals' midpoints and the weights of its inner samples")
+    return ops.sample_importance(z_vals, torch.nn.functional.pad(weights, (1, 1)), N_samples, merged=False)
+
+
+def raw2outputs_nerf_color(raw, z_vals, rays_d, occupancy=False, device="cuda:0"):
+    """src/common.py:204-245 → (depth, var, rgb, weights) on the HIP kernels.
+
+    Occupancy mode: `weights` is recomputed by the kernel's backward and not materialised; it is returned as
+    None (no caller on the NICE-SLAM path uses it: N_importance = 0).  Volume-density mode (iMAP*,
+    occupancy=False) returns weights [N,S] float32, without a gradient (its one reader, the importance
+    sampler, detaches its samples).
     """
     if not occupancy:
-        raise NotImplementedError("NICE-SLAM composites in occupancy mode (configs/nice_slam.yaml:5)")
+        return ops.composite_density(raw, z_vals, rays_d)
     depth, var, rgb = ops.composite(raw, z_vals)
     return depth, var, rgb, None
 

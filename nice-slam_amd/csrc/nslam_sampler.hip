@@ -260,3 +260,85 @@ extern "C" const char* nslam_strerror(int code) {
 // v9: nslam_cam_grad / nslam_cam_pose exports (they first shipped under v8 without a bump)
 // v24: nslam_track_best removed (superseded by nslam_loss_sum_best, v21, and nslam_cam_grad_step, v23)
 extern "C" int nslam_abi_version(void) { return 24; }
+
+// ------------------------------------------------------------------------------------------
+// Hierarchical sampler of iMAP* (src/common.py:19-63 with det=True, fused with the sort of Renderer.py:182-186).
+// One thread per ray: weights[1:-1] + 1e-5 -> pdf -> sequential float32 cdf (with the leading 0) over the
+// S - 1 bins z_mid; for each deterministic u the right-sided search, denom < 1e-5 -> 1, the sample in float64;
+// then the merge of the two ascending lists (finished by an insertion sort against ulp-level inversions,
+// as k_sample).
+// ------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kMaxSI = 256, kMaxNI = 128;
+
+__global__ __launch_bounds__(64) void k_sample_importance(const double* __restrict__ zv, const float* __restrict__ wts,
+                                                          const float* __restrict__ u, int64_t n, int S, int N,
+                                                          double* __restrict__ zout, double* __restrict__ zsamp) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const double* z = zv + r * (int64_t)S;
+  const float* w = wts + r * (int64_t)S;
+  const int nb = S - 1;  // bins (z_mid) = cdf entries
+  float cdf[kMaxSI];
+  float sum = 0.f;
+  for (int k = 1; k < S - 1; ++k) sum += w[k] + 1e-5f;
+  cdf[0] = 0.f;
+  float run = 0.f;
+  for (int k = 1; k < S - 1; ++k) {
+    run += (w[k] + 1e-5f) / sum;
+    cdf[k] = run;
+  }
+  double m[kMaxSI + kMaxNI];
+  double tmp[kMaxNI];  // the new samples, already ascending (u is a linspace)
+  int inds = 0;
+  for (int i = 0; i < N; ++i) {
+    const float ui = u[i];
+    while (inds < nb && cdf[inds] <= ui) ++inds;  // searchsorted(right=True); u ascends, so does inds
+    const int below = inds - 1 > 0 ? inds - 1 : 0;
+    const int above = inds < nb - 1 ? inds : nb - 1;
+    float denom = cdf[above] - cdf[below];
+    if (denom < 1e-5f) denom = 1.f;
+    const float t = (ui - cdf[below]) / denom;
+    const double b0 = 0.5 * (z[below + 1] + z[below]), b1 = 0.5 * (z[above + 1] + z[above]);
+    tmp[i] = b0 + (double)t * (b1 - b0);
+  }
+  if (zsamp) {
+    for (int k = 0; k < N; ++k) zsamp[r * (int64_t)N + k] = tmp[k];
+  }
+  if (!zout) return;
+  // merge z (ascending) and the new samples, back to front
+  int i = S - 1, j = N - 1;
+  for (int k = S + N - 1; k >= 0; --k) {
+    const bool take_b = i < 0 || (j >= 0 && tmp[j] >= z[i]);
+    m[k] = take_b ? tmp[j] : z[i];
+    j -= take_b ? 1 : 0;
+    i -= take_b ? 0 : 1;
+  }
+  for (int k = 1; k < S + N; ++k) {
+    const double v = m[k];
+    int q = k - 1;
+    while (q >= 0 && m[q] > v) {
+      m[q + 1] = m[q];
+      --q;
+    }
+    m[q + 1] = v;
+  }
+  double* out = zout + r * (int64_t)(S + N);
+  for (int k = 0; k < S + N; ++k) out[k] = m[k];
+}
+
+}  // namespace
+
+extern "C" int nslam_sample_importance(const double* z_vals, const float* weights, const float* u, int64_t n_rays,
+                                       int32_t n_samples, int32_t n_importance, double* z_out, double* z_samples,
+                                       void* stream) {
+  if (n_rays < 0 || n_samples < 3 || n_importance < 1) return NSLAM_EINVAL;
+  if (n_samples > kMaxSI || n_importance > kMaxNI) return NSLAM_EUNSUPPORTED;
+  if (n_rays == 0) return NSLAM_OK;
+  if (!z_vals || !weights || !u || (!z_out && !z_samples)) return NSLAM_EINVAL;
+  hipLaunchKernelGGL(k_sample_importance, dim3((unsigned)((n_rays + 63) / 64)), dim3(64), 0,
+                     reinterpret_cast<hipStream_t>(stream), z_vals, weights, u, n_rays, (int)n_samples,
+                     (int)n_importance, z_out, z_samples);
+  return hip_status();
+}

@@ -5,6 +5,9 @@ Mirrors src/conv_onet/models/decoder.py (GaussianFourierFeatureTransform :7-30, 
 load unchanged (`fc_c.i`, `pts_linears.i`, `output_linear`, `embedder._B`).  The forward pass is
 the fused HIP query (ops.query_points): one kernel evaluates the whole stage (grid lookups,
 Fourier features, the MLPs and the stage combiner) per 32-point tile.
+
+MLP with c_dim=0 is the iMAP* model (conv_onet/config.py:28-32): no grids, 256 wide, four blocks, (rgb, sigma)
+out; its forward is ops.imap_query (csrc/nslam_imap.hip).
 """
 from __future__ import annotations
 
@@ -55,6 +58,11 @@ class MLP(nn.Module):
     def __init__(self, name="", dim=3, c_dim=128, hidden_size=256, n_blocks=5, leaky=False, sample_mode="bilinear",
                  color=False, skips=[2], grid_len=0.16, pos_embedding_method="fourier", concat_feature=False):
         super().__init__()
+        self.imap = c_dim == 0
+        if self.imap:
+            self._init_imap(name, dim, hidden_size, n_blocks, leaky, color, skips, grid_len, pos_embedding_method,
+                            concat_feature, sample_mode)
+            return
         _check_supported(hidden_size, n_blocks, skips, leaky, sample_mode)
         if pos_embedding_method != "fourier" or dim != 3:
             raise NotImplementedError("NICE-SLAM uses the Fourier embedding (configs/nice_slam.yaml:116)")
@@ -82,20 +90,55 @@ class MLP(nn.Module):
         self.bound = None
         self._packer = None
 
+    def _init_imap(self, name, dim, hidden_size, n_blocks, leaky, color, skips, grid_len, pos_embedding_method,
+                   concat_feature, sample_mode):
+        """The iMAP* model, config.get_model(cfg, nice=False) (conv_onet/config.py): no feature grids, a
+        256-wide Fourier MLP of four blocks without skips that outputs (rgb, sigma)."""
+        if (dim != 3 or hidden_size != 256 or n_blocks != 4 or list(skips) != [] or leaky or not color
+                or pos_embedding_method != "fourier" or concat_feature):
+            raise NotImplementedError(
+                "with c_dim=0 the HIP decoder implements the iMAP* model only: MLP(name='', dim=3, c_dim=0, "
+                "color=True, hidden_size=256, skips=[], n_blocks=4, pos_embedding_method='fourier')")
+        self.name = name
+        self.color = True
+        self.no_grad_feature = False
+        self.c_dim = 0
+        self.grid_len = grid_len
+        self.concat_feature = False
+        self.n_blocks = n_blocks
+        self.skips = skips
+        self.embedder = GaussianFourierFeatureTransform(dim, mapping_size=93, scale=25)
+        self.pts_linears = nn.ModuleList([DenseLayer(93, hidden_size, activation="relu")]
+                                         + [DenseLayer(hidden_size, hidden_size, activation="relu")
+                                            for _ in range(n_blocks - 1)])
+        self.output_linear = DenseLayer(hidden_size, 4, activation="linear")
+        self.sample_mode = sample_mode
+        self.bound = None
+        self._packer = None
+
     def packer(self):
+        if self.imap:
+            raise NotImplementedError("the iMAP* decoder packs its weights on the device (ops.imap_query)")
         if self._packer is None:
             self._packer = DecoderPacker(self, kind=0, nc=2 if self.concat_feature else 1,
                                          nout=4 if self.color else 1)
         return self._packer
 
-    def forward(self, p, c_grid=None):
+    def forward(self, p, c_grid=None, oob_bound=None, **kwargs):
         """decoder.py:177-203 for this decoder alone (NICE.forward evaluates a whole stage in one
         fused launch instead): occupancy [P] (middle, fine) or [P, 4] (colour).
 
         Colour decoder: all four output columns are differentiable, as in the reference module —
         the 4th (which NICE.forward overwrites with the occupancy, decoder.py:341) reaches
         output_linear's row 3 through torch and the hidden layers, grid and points through the
-        kernels' h4 cotangent (ABI v17 nslam_query_cfg.g_h4; tests/test_gpu_decoders.py)."""
+        kernels' h4 cotangent (ABI v17 nslam_query_cfg.g_h4; tests/test_gpu_decoders.py).
+
+        iMAP* (c_dim=0): raw [P, 4] = (rgb, sigma) for p [P,3] or [1,P,3]; c_grid is ignored, and oob_bound
+        applies Renderer.eval_points' out-of-bound rule inside the kernel."""
+        if self.imap:
+            return ops.imap_query(ops.imap_params(self), p.reshape(-1, 3), oob_bound=oob_bound)
+        if oob_bound is not None or kwargs:
+            raise TypeError("oob_bound is an argument of the iMAP* decoder (c_dim=0) only")
         return ops.query_decoder(self, p, c_grid)
 
 

@@ -179,6 +179,7 @@ class Mapper(object):
         self.generator = generator
         self.stage = "middle"
         self.loss_history = None  # set to [] to record per-iteration losses (detached, no host sync)
+        self.regulation_draws = None  # iMAP* test hook: n_rays -> t_rand [n_rays, N_samples] (recorded jitter)
         self.fused = True   # optimize_map on engine.MappingEngine (False: the autograd drop-in)
         self.graphs = True  # fused path with device draws: each stage's iterations as one cached hipGraph
         self._eng = None
@@ -259,6 +260,9 @@ class Mapper(object):
                      keyframe_list, cur_c2w):
         """Mapping iterations (Mapper.py:230-540); returns the BA-updated cur_c2w or None."""
         self.calls += 1
+        if not self.nice:  # iMAP*: the autograd loop only (no fused engine, no graph capture)
+            return self._optimize_map_imap(num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
+                                           keyframe_dict, keyframe_list, cur_c2w)
         if self.fused:
             return self._optimize_map_fused(num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
                                             keyframe_dict, keyframe_list, cur_c2w)
@@ -776,3 +780,87 @@ class Mapper(object):
                 c2w = get_camera_from_tensor(cam_tensors[-1].detach())
                 cur_c2w = torch.cat([c2w, bottom], 0).clone()
         return cur_c2w
+
+    def _optimize_map_imap(self, num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
+                           keyframe_dict, keyframe_list, cur_c2w):
+        """optimize_map for iMAP* (the nice=False branches of Mapper.py:230-540), HIP ops under autograd: no
+        grids and no inside mask; every iteration is stage 'color' with the colour loss and the 0.0005 |sigma|
+        regulation term (Mapper.py:490-503); one Adam group over all decoder parameters at imap_decoders_lr
+        under StepLR(200, 0.8), plus the BA cameras at BA_cam_lr (Mapper.py:342-345, 380-389, 420-424)."""
+        H, W, fx, fy, cx, cy = self.H, self.W, self.fx, self.fy, self.cx, self.cy
+        cfg, device = self.cfg, self.device
+        bottom = torch.tensor([[0, 0, 0, 1.0]], dtype=torch.float32, device=device)
+        cur_gt_depth = cur_gt_depth.to(device)
+        cur_gt_color = cur_gt_color.to(device).float()
+        cur_c2w = cur_c2w.to(device)
+        optimize_frame, oldest_frame = self._select_window(keyframe_dict, keyframe_list, cur_gt_color, cur_gt_depth,
+                                                           cur_c2w)
+        pixs_per_image = self.mapping_pixels // len(optimize_frame)
+        params = list(self.decoders.parameters())
+        cam_tensors = []
+        if self.BA:
+            for frame in optimize_frame:
+                if frame != oldest_frame:
+                    c2w = keyframe_dict[frame]["est_c2w"] if frame != -1 else cur_c2w
+                    cam_tensors.append(get_tensor_from_camera(c2w).to(device).requires_grad_(True))
+        pg = [{"params": params, "lr": 0}]
+        if self.BA:
+            pg.append({"params": cam_tensors, "lr": 0})
+        optimizer = torch.optim.Adam(pg)
+        scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=200, gamma=0.8)
+        for joint_iter in range(num_joint_iters):
+            self.stage = "color"
+            optimizer.param_groups[0]["lr"] = cfg["mapping"]["imap_decoders_lr"]
+            if self.BA:
+                optimizer.param_groups[1]["lr"] = self.BA_cam_lr
+            ro_l, rd_l, gd_l, gc_l = [], [], [], []
+            cam_id = 0
+            for frame in optimize_frame:
+                if frame != -1:
+                    gt_depth, gt_color = self._frame_images(keyframe_dict[frame])
+                    if self.BA and frame != oldest_frame:
+                        c2w = get_camera_from_tensor(cam_tensors[cam_id])
+                        cam_id += 1
+                    else:
+                        c2w = keyframe_dict[frame]["est_c2w"].to(device)
+                else:
+                    gt_depth, gt_color = cur_gt_depth, cur_gt_color
+                    c2w = get_camera_from_tensor(cam_tensors[cam_id]) if self.BA else cur_c2w.to(device)
+                ro, rd, gd, gc = get_samples(0, H, 0, W, pixs_per_image, H, W, fx, fy, cx, cy, c2w, gt_depth,
+                                             gt_color, device, generator=self.generator)
+                ro_l.append(ro.float())
+                rd_l.append(rd.float())
+                gd_l.append(gd.float())
+                gc_l.append(gc.float())
+            rays_o, rays_d = torch.cat(ro_l), torch.cat(rd_l)
+            gt_d, gt_c = torch.cat(gd_l), torch.cat(gc_l)
+            depth, uncertainty, color = self.renderer.render_batch_ray(self.c, self.decoders, rays_d, rays_o, device,
+                                                                       self.stage, gt_depth=gt_d)
+            dm = gt_d > 0
+            loss = torch.abs(gt_d[dm] - depth[dm]).sum()
+            loss = loss + self.w_color_loss * torch.abs(gt_c - color).sum()
+            sigma = self.renderer.regulation(self.c, self.decoders, rays_d, rays_o, gt_d, device, self.stage,
+                                             generator=self.generator, t_rand=self._next_t_rand(gt_d.shape[0]))
+            loss = loss + 0.0005 * torch.abs(sigma).sum()
+            loss.backward(retain_graph=False)
+            if self.loss_history is not None:
+                self.loss_history.append(loss.detach())
+            optimizer.step()
+            scheduler.step()
+            optimizer.zero_grad()
+        if not self.BA:
+            return None
+        cam_id = 0
+        for frame in optimize_frame:
+            if frame != -1:
+                if frame != oldest_frame:
+                    c2w = get_camera_from_tensor(cam_tensors[cam_id].detach())
+                    keyframe_dict[frame]["est_c2w"] = torch.cat([c2w, bottom], 0).clone()
+                    cam_id += 1
+            else:
+                c2w = get_camera_from_tensor(cam_tensors[-1].detach())
+                cur_c2w = torch.cat([c2w, bottom], 0).clone()
+        return cur_c2w
+
+    def _next_t_rand(self, n_rays):
+        return self.regulation_draws(n_rays) if self.regulation_draws is not None else None

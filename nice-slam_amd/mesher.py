@@ -12,7 +12,10 @@ Deviations from the reference, all stated in DESIGN.md §7a:
     and returns the hull as half-spaces [M,4] (float64) rather than a trimesh object;
   * the hull test is a half-space test, trimesh's `contains` a ray test;
   * trimesh's vertex merging on construction (process=True) is not reproduced: the mesh is already indexed;
-  * iMAP*'s 'render_ray_along_normal' colour mode raises NotImplementedError.
+  * 'render_ray_along_normal' (iMAP*'s colour mode, Mesher.py:526-553) is implemented for nice=False: the vertex
+    normal is the normalised sum of the un-normalised cross products of the vertex's faces, which is believed to
+    be open3d's compute_vertex_normals; the library is absent, so that match is unpinned.  With nice=True the
+    mode still raises NotImplementedError.
 Extensions: get_mesh(..., mesh_bound=planes) skips the hull construction (no scipy needed), and the last
 extracted mesh stays on the object as `last_mesh`.
 """
@@ -126,8 +129,6 @@ class Mesher(object):
         self.bound = slam.bound
         self.nice = slam.nice
         self.verbose = slam.verbose
-        if not self.nice:
-            raise NotImplementedError("the HIP path implements NICE-SLAM (nice=True); iMAP* is out of scope")
 
         self.marching_cubes_bound = torch.from_numpy(
             np.array(cfg["mapping"]["marching_cubes_bound"]) * self.scale)
@@ -212,6 +213,34 @@ class Mesher(object):
                 for pi in torch.split(p, self.points_batch_size)]
         return torch.cat(rets, dim=0)
 
+    @staticmethod
+    def vertex_normals(vertices, faces):
+        """Unit vertex normals [V,3] float64: the sum over a vertex's faces of (v1 - v0) x (v2 - v0), un-normalised
+        (so weighted by area), then normalised; a vertex of no face (or of cancelling faces) gets (0, 0, 1)."""
+        v = vertices.double()
+        f = faces.long()
+        fn = torch.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]], dim=1)
+        n = torch.zeros_like(v)
+        for k in range(3):
+            n.index_add_(0, f[:, k], fn)
+        ln = n.norm(dim=1, keepdim=True)
+        up = torch.tensor([0.0, 0.0, 1.0], dtype=n.dtype, device=n.device).expand_as(n)
+        return torch.where(ln > 0, n / ln.clamp_min(1e-300), up)
+
+    def _colors_along_normal(self, vertices, faces, c, decoders, device, sign=-1.0, length=0.1):
+        """Mesher.py:526-553: the colour rendered along each vertex normal, from v - 0.1 n with gt_depth 0.1."""
+        normals = self.vertex_normals(vertices, faces)
+        rays_d = normals.to(device)
+        rays_o = (vertices.double() + sign * length * normals).to(device)
+        gt = torch.full((vertices.shape[0],), length, device=device)
+        cols = []
+        for i in range(0, rays_d.shape[0], self.ray_batch_size):
+            _, _, col = self.renderer.render_batch_ray(c, decoders, rays_d[i:i + self.ray_batch_size],
+                                                       rays_o[i:i + self.ray_batch_size], device, stage="color",
+                                                       gt_depth=gt[i:i + self.ray_batch_size])
+            cols.append(col)
+        return torch.cat(cols, 0) if cols else torch.zeros(0, 3, device=device)
+
     def get_grid_uniform(self, resolution):
         """Mesher.get_grid_uniform (Mesher.py:321-347): the lattice in np.meshgrid's default 'xy' order (y is
         the slowest axis of the flattened list) as float32 [R³,3], and the three float64 axes."""
@@ -237,10 +266,11 @@ class Mesher(object):
         """Mesher.get_mesh (Mesher.py:349-575): extract the mesh and write it to mesh_out_file (binary PLY).
 
         mesh_bound (extension): half-spaces [M,4] used instead of get_bound_from_frames."""
-        if color and self.color_mesh_extraction_method == "render_ray_along_normal":
+        along_normal = self.color_mesh_extraction_method == "render_ray_along_normal"
+        if color and along_normal and self.nice:
             raise NotImplementedError("'render_ray_along_normal' is iMAP*'s colour mode; the HIP path implements "
                                       "'direct_point_query'")
-        if color and self.color_mesh_extraction_method != "direct_point_query":
+        if color and not along_normal and self.color_mesh_extraction_method != "direct_point_query":
             raise ValueError(f"unknown color_mesh_extraction_method {self.color_mesh_extraction_method!r}")
         with torch.no_grad():
             grid = self.get_grid_uniform(self.resolution)
@@ -287,7 +317,10 @@ class Mesher(object):
 
             vertex_colors = None
             forecast_v = None
-            if color:
+            if color and along_normal and not show_forecast:
+                rgb = self._colors_along_normal(vertices, faces, c, decoders, device)
+                vertex_colors = (torch.clamp(rgb, 0, 1) * 255).to(torch.uint8)
+            elif color:
                 rgb = self.eval_points(vertices.float(), decoders, c, "color", device)[..., :3]
                 vertex_colors = (torch.clamp(rgb, 0, 1) * 255).to(torch.uint8)
                 if show_forecast:  # cyan for the forecast region

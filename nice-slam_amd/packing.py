@@ -176,3 +176,34 @@ class DecoderPacker:
         """flat gradient buffer → per-parameter views (named_parameters order)."""
         return [flat_grad[self.offsets[n]:self.offsets[n] + int(np.prod(self.shapes[n]))].view(self.shapes[n])
                 for n in self.names]
+
+
+# ----------------------------------------------------------------------------------------------
+# iMAP* (csrc/nslam_imap.hip): the 256-wide layers as K-major fragment streams
+# ----------------------------------------------------------------------------------------------
+IMAP_HIDDEN = 256
+IMAP_PACKED = 2 * (8 * 12 * 256 + 3 * 8 * 32 * 256)  # floats; equals nslam_imap_packed_size() / 4
+
+
+def imap_fragments(weights):
+    """The packed fragment buffer nslam_imap_pack writes, restated in numpy from pts_linears' four weight
+    matrices ([256,93], [256,256] x3; float32).
+
+    A matrix M[R][K] (R rows in blocks of 32, K padded to a multiple of 8) is stored as
+      frag[((ob * K/8 + s4) * 64 + lane) * 4 + j] = M[32 ob + (lane & 31)][2 (4 s4 + j) + (lane >> 5)]
+    i.e. for output block ob one 16-byte load per lane covers four consecutive v_mfma_f32_32x32x2_f32 steps (the A
+    operand of step s is row lane & 31, K index 2s + (lane >> 5)).  Order: the forward matrices W0 (K 93 → 96),
+    W1..W3, then the transposed ones W0^T (rows 93 → 96), W1^T..W3^T.  The device kernel is the product path; this
+    restatement documents the layout and checks it (tests/test_gpu_imap.py)."""
+    def frag(M, R, K):
+        Mp = np.zeros((R, K), dtype=np.float32)
+        Mp[:M.shape[0], :M.shape[1]] = M
+        ob, s4, lane, j = np.meshgrid(np.arange(R // 32), np.arange(K // 8), np.arange(64), np.arange(4), indexing="ij")
+        return Mp[32 * ob + (lane & 31), 2 * (4 * s4 + j) + (lane >> 5)].reshape(-1)
+
+    ws = [np.asarray(w, dtype=np.float32) for w in weights]
+    out = [frag(ws[0], 256, 96)] + [frag(w, 256, 256) for w in ws[1:]]
+    out += [frag(ws[0].T, 96, 256)] + [frag(w.T, 256, 256) for w in ws[1:]]
+    out = np.concatenate(out)
+    assert out.size == IMAP_PACKED
+    return out

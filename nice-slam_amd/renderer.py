@@ -2,6 +2,10 @@
 
 render_batch_ray = sampler kernel (float64 z) → pts = o + d·z (torch, float64, differentiable in
 the rays) → fused query kernel (grid lookups + decoders + OOB logit) → compositing kernel.
+
+iMAP* (nice=False, occupancy=False, N_importance > 0; configs/imap.yaml): the query is the 256-wide MLP
+kernel, compositing is the volume-density kernel, and a second pass renders the coarse samples merged with the
+importance sampler's (Renderer.py:181-196).
 """
 from __future__ import annotations
 
@@ -26,14 +30,18 @@ class Renderer(object):
         self.nice = slam.nice
         self.bound = slam.bound
         self.H, self.W, self.fx, self.fy, self.cx, self.cy = slam.H, slam.W, slam.fx, slam.fy, slam.cx, slam.cy
-        if not self.nice or not self.occupancy:
-            raise NotImplementedError("the HIP path implements NICE-SLAM (nice=True, occupancy=True); iMAP* is "
-                                      "out of scope")
-        if self.perturb > 0 or self.N_importance > 0:
-            raise NotImplementedError("NICE-SLAM renders with perturb=0, N_importance=0 (configs/nice_slam.yaml)")
+        if self.nice == (not self.occupancy):
+            raise NotImplementedError("the HIP path implements NICE-SLAM (nice=True, occupancy=True) and iMAP* "
+                                      "(nice=False, occupancy=False), not their mixtures")
+        if self.perturb > 0:
+            raise NotImplementedError("perturb > 0 (random sample_pdf draws): no configuration sets it")
+        if self.nice and self.N_importance > 0:
+            raise NotImplementedError("NICE-SLAM renders with N_importance=0 (configs/nice_slam.yaml)")
 
     def eval_points(self, p, decoders, c=None, stage="color", device="cuda:0"):
         """Renderer.eval_points (Renderer.py:23-61): raw [M,4]; OOB points get occupancy logit 100."""
+        if not self.nice:
+            return decoders(p, c_grid=None, oob_bound=self.bound)
         return decoders(p, c_grid=c, stage=stage, oob_bound=self.bound)
 
     def render_batch_ray(self, c, decoders, rays_d, rays_o, device, stage, gt_depth=None, gt_max=None):
@@ -49,8 +57,38 @@ class Renderer(object):
         pts = rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]
         raw = self.eval_points(pts.reshape(-1, 3), decoders, c, stage, device)
         raw = raw.reshape(n_rays, z.shape[1], 4)
-        depth, uncertainty, color = ops.composite(raw, z)
+        if self.occupancy:
+            depth, uncertainty, color = ops.composite(raw, z)
+            return depth, uncertainty, color
+        depth, uncertainty, color, weights = ops.composite_density(raw, z, rays_d)
+        if self.N_importance > 0:  # Renderer.py:181-196
+            z = ops.sample_importance(z, weights, self.N_importance)
+            pts = rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]
+            raw = self.eval_points(pts.reshape(-1, 3), decoders, c, stage, device)
+            raw = raw.reshape(n_rays, z.shape[1], 4)
+            depth, uncertainty, color, _ = ops.composite_density(raw, z, rays_d)
         return depth, uncertainty, color
+
+    def regulation(self, c, decoders, rays_d, rays_o, gt_depth, device, stage="color", generator=None, t_rand=None):
+        """Renderer.regulation (Renderer.py:258-296, iMAP* only): sigma [N * N_samples] at stratified-jittered
+        samples between the camera and 0.85 * depth.
+
+        The jitter is torch.rand on `device` from `generator`, or t_rand [N, N_samples] (extension: recorded
+        draws)."""
+        gt = gt_depth.reshape(-1, 1).repeat(1, self.N_samples)
+        t_vals = torch.linspace(0., 1., steps=self.N_samples).to(device)
+        near = 0.0
+        far = gt * 0.85
+        z_vals = near * (1. - t_vals) + far * t_vals
+        mids = .5 * (z_vals[..., 1:] + z_vals[..., :-1])
+        upper = torch.cat([mids, z_vals[..., -1:]], -1)
+        lower = torch.cat([z_vals[..., :1], mids], -1)
+        if t_rand is None:
+            t_rand = torch.rand(z_vals.shape, device=device, generator=generator)
+        z_vals = lower + (upper - lower) * t_rand.to(device)
+        pts = rays_o[..., None, :] + rays_d[..., None, :] * z_vals[..., :, None]
+        raw = self.eval_points(pts.reshape(-1, 3), decoders, c, stage, device)
+        return raw[:, -1]
 
     def render_img(self, c, decoders, c2w, device, stage, gt_depth=None):
         """Renderer.render_img (Renderer.py:200-255): forward-only full-image render in ray batches."""

@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .decoder import NICE
+from .decoder import MLP, NICE
 
 
 def update_cam(cfg):
@@ -63,8 +63,14 @@ def grid_init(cfg, bound, device="cuda:0", coarse=None, generator=None):
     return out
 
 
-def build_decoders(cfg, bound, device="cuda:0"):
-    """config.get_model + load_bound's decoder wiring (src/conv_onet/config.py:4-33, NICE_SLAM.py:151-157)."""
+def build_decoders(cfg, bound, device="cuda:0", nice=True):
+    """config.get_model + load_bound's decoder wiring (src/conv_onet/config.py:4-33, NICE_SLAM.py:151-157).
+
+    nice=False: the iMAP* model (config.py:28-32), which reads no grid and has no bound of its own."""
+    if not nice:
+        dec = MLP(name="", dim=cfg["data"]["dim"], c_dim=0, color=True, hidden_size=256, skips=[], n_blocks=4,
+                  pos_embedding_method=cfg["model"]["pos_embedding_method"])
+        return dec.to(device)
     gl = cfg["grid_len"]
     dec = NICE(dim=cfg["data"]["dim"], c_dim=cfg["model"]["c_dim"], coarse=cfg["coarse"],
                coarse_grid_len=gl["coarse"], middle_grid_len=gl["middle"], fine_grid_len=gl["fine"],
@@ -76,17 +82,18 @@ def build_decoders(cfg, bound, device="cuda:0"):
 class SlamState:
     """What Renderer / Tracker / Mapper read from the reference's NICE_SLAM object."""
 
-    def __init__(self, cfg, device="cuda:0", n_img=1, generator=None):
+    def __init__(self, cfg, device="cuda:0", n_img=1, generator=None, nice=True):
         self.cfg = cfg
-        self.nice = True
+        self.nice = nice
         self.coarse = cfg["coarse"]
         self.occupancy = cfg["occupancy"]
         self.verbose = cfg.get("verbose", False)
         self.low_gpu_mem = cfg.get("low_gpu_mem", False)
         self.H, self.W, self.fx, self.fy, self.cx, self.cy = update_cam(cfg)
         self.bound = load_bound(cfg)
-        self.shared_decoders = build_decoders(cfg, self.bound, device)
-        self.shared_c = grid_init(cfg, self.bound, device, generator=generator)
+        self.shared_decoders = build_decoders(cfg, self.bound, device, nice=nice)
+        # iMAP* has no feature grids (NICE_SLAM.py:56-57 calls grid_init for nice only)
+        self.shared_c = grid_init(cfg, self.bound, device, generator=generator) if nice else {}
         self.estimate_c2w_list = torch.zeros((n_img, 4, 4))
         self.gt_c2w_list = torch.zeros((n_img, 4, 4))
         self.idx = torch.zeros((1)).int()

@@ -64,6 +64,8 @@ class Tracker(object):
         self._fstate = None   # persistent buffers of the captured camera loop
         self._graphs = {}
         self._draw_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        if not self.nice:  # iMAP*: the autograd camera loop (the fused engine evaluates the NICE decoders)
+            self.fused = False
 
     def _inside_mask(self, rays_o, rays_d, gt_depth):
         """Tracker.py:95-100: keep rays whose AABB exit distance >= gt depth."""
