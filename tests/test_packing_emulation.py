@@ -55,7 +55,15 @@ def packed_numpy(packer, module):
 @pytest.fixture(scope="module")
 def nice(pkg):
     torch.manual_seed(0)
-    return pkg.NICE(c_dim=32, coarse=True, hidden_size=32, coarse_grid_len=2.0, middle_grid_len=0.32)
+    m = pkg.NICE(c_dim=32, coarse=True, hidden_size=32, coarse_grid_len=2.0, middle_grid_len=0.32)
+    # the initialisation law leaves every pts_linears / output_linear bias at zero, where a wrong Bias / Bo index
+    # map cannot show: draw them as a trained decoder has them
+    with torch.no_grad():
+        for k, p in m.named_parameters():
+            if k.endswith(".bias") and (".pts_linears." in k or ".output_linear." in k):
+                p.normal_(0.0, 0.3)
+                assert bool((p != 0).all()), k
+    return m
 
 
 @pytest.mark.parametrize("name", ["middle", "fine", "color"])
