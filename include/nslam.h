@@ -724,7 +724,9 @@ int nslam_imap_bwd(const nslam_imap_params* params, const float* packed, const n
  *   alpha_k = 1 - exp(-relu(raw_k[3]) dists_k);  T_k = prod_(j<k) (1 - alpha_j + 1e-10);  w_k = alpha_k T_k
  *   rgb = sum w_k raw_k[:3] (f32);  depth = sum w_k z_k (f64);  var = sum w_k (z_k - depth)^2 (f64)
  * weights [n][S] float32 (may be NULL) is what the importance sampler reads.  The backward writes g_raw
- * [n][S][4] and, when not NULL, g_rays_d [n][3] (the norm factor's edge).  S <= 256. */
+ * [n][S][4] and, when not NULL, g_rays_d [n][3] (the norm factor's edge).  2 <= S <= 256: S = 1 is
+ * NSLAM_EUNSUPPORTED (the reference builds the trailing 1e10 from an empty slice there and composites no sample;
+ * one opaque sample, which these kernels would compute, is not its answer). */
 int nslam_composite_density_fwd(const float* raw, const double* z_vals, const float* rays_d, int64_t n_rays,
                                 int32_t n_samples, double* depth, double* var, float* color, float* weights,
                                 void* stream);

@@ -519,7 +519,9 @@ __device__ __forceinline__ DSample load_dsample(const float* raw, const double* 
   s.dist0 = (k < S - 1) ? (float)(z[k + 1] - s.z) : 1e10f;
   const float dist = s.dist0 * norm;
   s.sig = s.raw[3] > 0.f ? s.raw[3] : 0.f;
-  s.e = act ? expf(-(s.sig * dist)) : 1.f;
+  // the correctly rounded exponential of the float32 argument: the factors of a transparent ray are e itself,
+  // so a mean error of expf near 1 adds up linearly along a 256-sample transmittance product
+  s.e = act ? (float)exp(-(double)(s.sig * dist)) : 1.f;
   s.a = 1.f - s.e;
   s.f = act ? (1.f - s.a) + 1e-10f : 1.f;
   const float incl = wave_prefix_prod(s.f, lane);
@@ -671,7 +673,8 @@ extern "C" int nslam_composite_density_fwd(const float* raw, const double* z_val
                                            int32_t n_samples, double* depth, double* var, float* color,
                                            float* weights, void* stream) {
   if (n_rays < 0 || n_samples <= 0) return NSLAM_EINVAL;
-  if (n_samples > kMaxS) return NSLAM_EUNSUPPORTED;
+  // one sample: the reference sizes the trailing 1e10 from an empty slice of z differences and composites nothing
+  if (n_samples > kMaxS || n_samples < 2) return NSLAM_EUNSUPPORTED;
   if (n_rays == 0) return NSLAM_OK;
   if (!raw || !z_vals || !rays_d || !depth || !var || !color) return NSLAM_EINVAL;
   const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
@@ -684,7 +687,8 @@ extern "C" int nslam_composite_density_bwd(const float* raw, const double* z_val
                                            int32_t n_samples, const double* g_depth, const double* g_var,
                                            const float* g_color, float* g_raw, float* g_rays_d, void* stream) {
   if (n_rays < 0 || n_samples <= 0) return NSLAM_EINVAL;
-  if (n_samples > kMaxS) return NSLAM_EUNSUPPORTED;
+  // one sample: the reference sizes the trailing 1e10 from an empty slice of z differences and composites nothing
+  if (n_samples > kMaxS || n_samples < 2) return NSLAM_EUNSUPPORTED;
   if (n_rays == 0) return NSLAM_OK;
   if (!raw || !z_vals || !rays_d || !g_raw) return NSLAM_EINVAL;
   const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);

@@ -9,7 +9,8 @@
 //   z_vals = sort(cat[z, z_surface])                                  (:168-170)
 // The two lists are monotone in their index, so the sort is a two-way merge (each list reversed
 // first if it is descending).  Dtype promotions follow the reference exactly (no FMA contraction:
-// the library is built with -ffp-contract=off).
+// the library is built with -ffp-contract=off).  With lindisp the reference produces NaN (inf * 0) in
+// rows whose gt_depth or far is 0; torch.sort puts NaN last, and so do both kernels.
 #include "nslam_dev.h"
 
 namespace {
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(128) void k_sample(SamplerArgs a) {
   for (int k = 0; k < s0 + s1; ++k) {
     const double va = i < s0 ? zs[rev0 ? s0 - 1 - i : i] : 0.0;
     const double vb = j < s1 ? zu[rev1 ? s1 - 1 - j : j] : 0.0;
-    const bool take_a = (j >= s1) || (i < s0 && va <= vb);
+    const bool take_a = (j >= s1) || (i < s0 && (va <= vb || vb != vb));  // a NaN orders after every number
     m[k] = take_a ? va : vb;
     i += take_a ? 1 : 0;
     j += take_a ? 0 : 1;
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(128) void k_sample(SamplerArgs a) {
   for (int k = 1; k < s0 + s1; ++k) {
     const double v = m[k];
     int q = k - 1;
-    while (q >= 0 && m[q] > v) {
+    while (q >= 0 && (m[q] > v || (m[q] != m[q] && v == v))) {  // (torch.sort puts NaN last)
       m[q + 1] = m[q];
       --q;
     }
@@ -185,7 +186,8 @@ __global__ __launch_bounds__(256) void k_sample_wave(SamplerArgs a) {
   const int v_lo = __double2loint(v), v_hi = __double2hiint(v);
   for (int j = 0; j < S; ++j) {  // lane j's value by v_readlane (j is uniform): no LDS round trip per step
     const double vj = __hiloint2double(__builtin_amdgcn_readlane(v_hi, j), __builtin_amdgcn_readlane(v_lo, j));
-    rank += (vj < v || (vj == v && j < lane)) ? 1 : 0;
+    // a NaN (lindisp: inf * 0 where gt_depth or far is 0) ranks after every number, NaNs among themselves by lane
+    rank += (vj < v || (vj == v && j < lane) || (v != v && (vj == vj || j < lane))) ? 1 : 0;
   }
   if (lane < S) out[rank] = v;
 }

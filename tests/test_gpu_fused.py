@@ -4,7 +4,10 @@ and torch on the same inputs:
   nslam_gather_rays  vs common.get_samples (torch on the device, the reference's code path) and the
                         oracle's inside mask (Mapper.py:469-481)          — bit-exact
   ray-form query     vs the pts-form query (pts = o + d·z in torch)       — bit-exact
-  nslam_render_loss  vs composite + the reference loss through autograd   — mapper and tracker
+  nslam_render_loss  vs the project's own compositor (ops.composite: the same load_sample / ray_bwd device
+                        code) + the reference loss through autograd       — mapper and tracker; this pins the
+                        fusion, not the compositing: the independent float64 check is
+                        test_gpu_ray_edges.py::test_render_loss_vs_float64
   nslam_adam_step    vs torch.optim.Adam(foreach=False) (dense, row-masked, per-parameter steps)
   MappingEngine      vs the autograd path (one iteration's gradients; loss decreases over 5)
 """
@@ -136,6 +139,10 @@ def _autograd_loss(raw, z, gd, gc, keep, mode, use_color, handle_dynamic, w):
                                                      ("tracker", True, False, 100), ("tracker", True, True, 400),
                                                      ("tracker", True, True, 60)])
 def test_render_loss_matches_autograd(tiny, mode, use_color, hd, n_per):
+    """The fused loss against ops.composite + the reference's loss under autograd.  Both sides run the same
+    compositing device code, so an error there cancels: this checks the fusion (masks, median, cotangents).
+    The compositing itself is checked against a float64 reference that shares no code with the kernels in
+    test_gpu_ray_edges.py::test_render_loss_vs_float64."""
     sc, frames = _frames(tiny)
     nice, c = _nice(sc)
     pix = torch.randint(96 * 128, (3 * n_per,), device=DEV, generator=torch.Generator(device=DEV).manual_seed(4))
