@@ -657,6 +657,23 @@ size_t nslam_raster_workspace_size(int64_t capacity);
 int nslam_undistort_u8(const uint8_t* src, int32_t H, int32_t W, int32_t C, double fx, double fy, double cx,
                        double cy, const double dist[5], uint8_t* dst, void* stream);
 
+/* The visualiser's six panels (src/utils/Visualizer.py:57-100; additive, csrc/nslam_vis.hip) as one interleaved
+ * uint8 image out [2H][3W][3], written whole on the device:
+ *   row 0: input depth | generated depth | depth residual     row 1: input RGB | generated RGB | RGB residual
+ * gt_depth [H][W] float32, gt_color [H][W][3] float32, depth [H][W] float64 and color [H][W][3] float32 (what
+ * render_img returns), vmax a DEVICE float32 scalar (max(gt_depth), an ordinary reduction: no host sync).
+ * Residuals are |gt - rendered| (depth in float64, colour in float32), zero where gt_depth == 0.
+ * Depth panels are matplotlib's Normalize(0, vmax) then Colormap.__call__(bytes=True) of "plasma", on the value
+ * v as a float64:  t = (vmax == 0 ? 0 : v / vmax) * 256;  NaN -> (0, 0, 0);  t < 0 -> row 0;  t >= 256 -> row 255
+ * (v == vmax lands there, as matplotlib moves it; so does anything above);  else row (int)t   of the 256 x 3 byte
+ * table csrc/nslam_plasma_lut.h (generated from matplotlib by tools/gen_plasma_lut.py).
+ * RGB panels are floor(255 * clip(v, 0, 1) + 0.5) in float32 without FMA contraction, NaN as 0: this project's
+ * own rule, not pinned to matplotlib's internal image conversion.
+ * One thread per output pixel, one launch, no host synchronisation.  NSLAM_EINVAL: a null pointer or a negative
+ * size.  An empty image is NSLAM_OK without a launch.  NSLAM_EUNSUPPORTED: 6*H*W >= 2^31. */
+int nslam_vis_panels(const float* gt_depth, const float* gt_color, const double* depth, const float* color,
+                     int32_t H, int32_t W, const float* vmax, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * iMAP* (configs/imap.yaml, run.py --imap; additive, no ABI bump): the 256-wide Fourier MLP
  * (csrc/nslam_imap.hip), volume-density compositing (csrc/nslam_composite.hip) and the hierarchical sampler

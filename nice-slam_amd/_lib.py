@@ -163,6 +163,8 @@ EXPORTS = (
     "nslam_imap_packed_size", "nslam_imap_pack", "nslam_imap_tape_size", "nslam_imap_fwd",
     "nslam_imap_bwd_workspace_size", "nslam_imap_bwd", "nslam_composite_density_fwd",
     "nslam_composite_density_bwd", "nslam_sample_importance",
+    # the visualiser's panel mosaic (additive: no ABI bump)
+    "nslam_vis_panels",
 )
 
 _lib = None
@@ -286,6 +288,7 @@ def lib():
         L.nslam_composite_density_fwd.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
         L.nslam_composite_density_bwd.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
         L.nslam_sample_importance.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
+        L.nslam_vis_panels.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L

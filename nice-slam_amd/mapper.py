@@ -22,9 +22,12 @@ Differences from the reference (none changes the maths):
     iterations are captured ONCE in a hipGraph and replayed by every later call of the same shape
     (the window's frames are copied into persistent slots, the frustum selection is bound on the
     device with capacity-sized buffers: engine.MappingEngine.bind_masks).
-The mapping loop driver (Mapper.run, Mapper.py:542-657) is out of scope (dataset/meshing/ckpt glue).
+One pass of the mapping loop driver (Mapper.run, Mapper.py:572-654) is `map_frame`; NICE_SLAM.run schedules it
+serially (nice_slam.py).
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -432,7 +435,7 @@ class Mapper(object):
         for d in eng.decs.values():  # parameters may have been assigned since the last call
             d.repack()
         device_draws = _common.select_uv is _SELECT_UV and self.generator is None
-        use_graphs = self.graphs and device_draws
+        use_graphs = self.graphs and device_draws and self._iter_hook is None  # (a hooked call runs eagerly)
         # Everything that does not depend on the keyframe selection is enqueued first: the selection reads
         # its overlap scores back to the host (the reference's numpy ranking), and what is queued before
         # that read overlaps the previous call's iterations still running on the device: this call's
@@ -487,6 +490,7 @@ class Mapper(object):
             optimize_frame, oldest_frame = self._select_window(keyframe_dict, keyframe_list, cur_gt_color,
                                                                cur_gt_depth, cur_c2w)
         mark("selected")
+        self._record_selected(idx, optimize_frame, keyframe_dict, keyframe_list, gt_cur_c2w, cur_c2w)
         F = len(optimize_frame)
         n_per = self.mapping_pixels // F
         # window slots: the oldest frame (fixed under BA) first, then the others in optimize_frame order
@@ -613,11 +617,15 @@ class Mapper(object):
         else:
             if ncam:
                 cams_init()
+            joint_iter = 0
             for stg, n in runs:
                 self.stage = stg
                 set_lr(stg)
                 eng._pre = None
                 for _ in range(n):
+                    if self._iter_hook is not None:  # (Mapper.py:426-428: before the iteration's work)
+                        self._iter_hook(joint_iter)
+                    joint_iter += 1
                     iteration(stg, None if hist is None else (lambda rl: hist.append(rl.sum())))
         mark("iterations")
         if tm is not None:
@@ -658,9 +666,10 @@ class Mapper(object):
             optimize_frame = optimize_frame + [len(keyframe_list) - 1]
             oldest_frame = min(optimize_frame)
         optimize_frame += [-1]
+        self._record_selected(idx, optimize_frame, keyframe_dict, keyframe_list, gt_cur_c2w, cur_c2w)
         pixs_per_image = self.mapping_pixels // len(optimize_frame)
 
-        groups = {"decoders": [], "coarse": [], "middle": [], "fine": [], "color": []}
+        groups ={"decoders": [], "coarse": [], "middle": [], "fine": [], "color": []}
         masked = {}
         for key, val in c.items():
             if self.frustum_feature_selection:
@@ -719,6 +728,8 @@ class Mapper(object):
                 optimizer.param_groups[gi]["lr"] = st[name + "_lr"] * lr_factor
             if self.BA and self.stage == "color":
                 optimizer.param_groups[5]["lr"] = self.BA_cam_lr
+            if self._iter_hook is not None:
+                self._iter_hook(joint_iter)
 
             optimizer.zero_grad()
             ro_l, rd_l, gd_l, gc_l = [], [], [], []
@@ -795,6 +806,7 @@ class Mapper(object):
         cur_c2w = cur_c2w.to(device)
         optimize_frame, oldest_frame = self._select_window(keyframe_dict, keyframe_list, cur_gt_color, cur_gt_depth,
                                                            cur_c2w)
+        self._record_selected(idx, optimize_frame, keyframe_dict, keyframe_list, gt_cur_c2w, cur_c2w)
         pixs_per_image = self.mapping_pixels // len(optimize_frame)
         params = list(self.decoders.parameters())
         cam_tensors = []
@@ -813,6 +825,8 @@ class Mapper(object):
             optimizer.param_groups[0]["lr"] = cfg["mapping"]["imap_decoders_lr"]
             if self.BA:
                 optimizer.param_groups[1]["lr"] = self.BA_cam_lr
+            if self._iter_hook is not None:
+                self._iter_hook(joint_iter)
             ro_l, rd_l, gd_l, gc_l = [], [], [], []
             cam_id = 0
             for frame in optimize_frame:
@@ -861,6 +875,155 @@ class Mapper(object):
                 c2w = get_camera_from_tensor(cam_tensors[-1].detach())
                 cur_c2w = torch.cat([c2w, bottom], 0).clone()
         return cur_c2w
+
+    # -- the frame loop (Mapper.run, Mapper.py:542-657) --------------------------------------------
+    _iter_hook = None  # map_frame(): called as hook(joint_iter) before each mapping iteration (the visualiser)
+    save_selected_keyframes_info = False  # (attach_run reads the config's)
+
+    def _record_selected(self, idx, optimize_frame, keyframe_dict, keyframe_list, gt_cur_c2w, cur_c2w):
+        """Mapper.py:274-287: the call's window as selected_keyframes[idx]."""
+        if not self.save_selected_keyframes_info:
+            return
+        info = []
+        for frame in optimize_frame:
+            if frame != -1:
+                info.append({"idx": keyframe_list[frame], "gt_c2w": keyframe_dict[frame]["gt_c2w"],
+                             "est_c2w": keyframe_dict[frame]["est_c2w"]})
+            else:
+                info.append({"idx": idx, "gt_c2w": gt_cur_c2w, "est_c2w": cur_c2w})
+        self.selected_keyframes[idx] = info
+
+    def attach_run(self, slam):
+        """What Mapper.__init__ (Mapper.py:23-92) takes from `slam` and cfg for the frame loop, and the mapping
+        visualiser.  NICE_SLAM calls it once; optimize_map alone does not need it."""
+        from .visualizer import Visualizer
+        cfg, m = self.cfg, self.cfg["mapping"]
+        self.idx = slam.idx
+        self.logger = slam.logger
+        self.mesher = slam.mesher
+        self.output = slam.output
+        self.verbose = slam.verbose
+        self.low_gpu_mem = slam.low_gpu_mem
+        self.mapping_idx = slam.mapping_idx
+        self.mapping_cnt = slam.mapping_cnt
+        self.mapping_first_frame = slam.mapping_first_frame
+        self.n_img = slam.n_img
+        self.pose_work = slam.pose_work
+        self.mirror_poses = slam.mirror_poses
+        self.sync_method = cfg["sync_method"]
+        self.eval_rec = cfg["meshing"]["eval_rec"]
+        self.clean_mesh = cfg["meshing"]["clean_mesh"]
+        self.mesh_coarse_level = cfg["meshing"]["mesh_coarse_level"]
+        self.mesh_freq, self.ckpt_freq = m["mesh_freq"], m["ckpt_freq"]
+        self.every_frame, self.keyframe_every = m["every_frame"], m["keyframe_every"]
+        self.color_refine = m["color_refine"]
+        self.no_vis_on_first_frame = m["no_vis_on_first_frame"]
+        self.no_log_on_first_frame = m["no_log_on_first_frame"]
+        self.no_mesh_on_first_frame = m["no_mesh_on_first_frame"]
+        self.save_selected_keyframes_info = m["save_selected_keyframes_info"]
+        if self.save_selected_keyframes_info:
+            self.selected_keyframes = {}
+        self.visualizer = None
+        if "Demo" not in self.output:  # Mapper.py:87-91: no mapping visualiser in the demo
+            self.visualizer = Visualizer(freq=m["vis_freq"], inside_freq=m["vis_inside_freq"],
+                                         vis_dir=os.path.join(self.output, "mapping_vis"), renderer=self.renderer,
+                                         verbose=self.verbose, device=self.device)
+        self._init = True
+
+    def map_frame(self, idx, gt_color, gt_depth, gt_c2w):
+        """One pass of Mapper.run's loop body (Mapper.py:572-654) for frame idx; True when it was the last.
+
+        The colour-refinement pass mutates the live Mapper as the reference does (window ×2, both ratios 0,
+        fix_color, frustum selection off).  The stage graphs' keys cover the window, the schedule and the
+        trainable decoders, and the window slots regrow by size; the cached optimiser (its decoder group was
+        built with the colour decoder in it) and the captured per-call setup (it captured the frustum kernel) do
+        not see the change, so both are dropped there, with the graphs bound to them.
+
+        On a frame whose mapping visualisation fires, optimize_map runs its eager fused path with the visualiser
+        called before every iteration, where Mapper.py:426-428 has it; the first frame's one-off schedule
+        (iters_first) runs eagerly too; every other frame replays the graphs."""
+        import shutil
+        idx = int(idx)
+        cfg = self.cfg
+        est = self.pose_work
+        if self.verbose:
+            print(("Coarse " if self.coarse_mapper else "") + "Mapping Frame ", idx)
+        if idx == 0 and self._init:
+            est[0] = gt_c2w.to(est.device)  # Mapper.py:546
+        if not self._init:
+            lr_factor = cfg["mapping"]["lr_factor"]
+            num_joint_iters = cfg["mapping"]["iters"]
+            if idx == self.n_img - 1 and self.color_refine and not self.coarse_mapper:
+                outer_joint_iters = 5
+                self.mapping_window_size *= 2
+                self.middle_iter_ratio = 0.0
+                self.fine_iter_ratio = 0.0
+                num_joint_iters *= 5
+                self.fix_color = True
+                self.frustum_feature_selection = False
+                self._fopt = None
+                self._graphs.clear()
+            else:
+                outer_joint_iters = 1 if self.nice else 3
+        else:
+            outer_joint_iters = 1
+            lr_factor = cfg["mapping"]["lr_first_factor"]
+            num_joint_iters = cfg["mapping"]["iters_first"]
+        cur_c2w = est[idx].to(self.device).clone()
+        num_joint_iters = num_joint_iters // outer_joint_iters
+        vis = self.visualizer
+        if vis is not None and not (idx == 0 and self.no_vis_on_first_frame) and idx % vis.freq == 0:
+            self._iter_hook = lambda it: vis.vis(idx, it, gt_depth, gt_color, self._hook_c2w, self.c, self.decoders)
+        graphs = self.graphs
+        if self._init:  # the first frame's schedule (iters_first) runs once: a graph of it would never be replayed
+            self.graphs = False
+        try:
+            for outer_joint_iter in range(outer_joint_iters):
+                self.BA = (len(self.keyframe_list) > 4) and cfg["mapping"]["BA"] and (not self.coarse_mapper)
+                self._hook_c2w = cur_c2w
+                _ = self.optimize_map(num_joint_iters, lr_factor, idx, gt_color, gt_depth, gt_c2w, self.keyframe_dict,
+                                      self.keyframe_list, cur_c2w=cur_c2w)
+                if self.BA:
+                    cur_c2w = _
+                    est[idx] = cur_c2w.to(est.device)
+                if outer_joint_iter == outer_joint_iters - 1:
+                    if (idx % self.keyframe_every == 0 or idx == self.n_img - 2) and idx not in self.keyframe_list:
+                        self.keyframe_list.append(idx)
+                        self.keyframe_dict.append({"gt_c2w": gt_c2w.cpu(), "idx": idx, "color": gt_color.cpu(),
+                                                   "depth": gt_depth.cpu(), "est_c2w": cur_c2w.clone()})
+        finally:
+            self._iter_hook = None
+            self.graphs = graphs
+        if self.low_gpu_mem:
+            torch.cuda.empty_cache()
+        self._init = False
+        self.mapping_first_frame[0] = 1
+        last = idx == self.n_img - 1
+        if not self.coarse_mapper:
+            if ((not (idx == 0 and self.no_log_on_first_frame)) and idx % self.ckpt_freq == 0) or last:
+                self.mirror_poses()
+                self.logger.log(idx, self.keyframe_dict, self.keyframe_list,
+                                selected_keyframes=self.selected_keyframes if self.save_selected_keyframes_info
+                                else None)
+            self.mapping_idx[0] = idx
+            self.mapping_cnt[0] += 1
+            out = f"{self.output}/mesh"
+            kw = dict(clean_mesh=self.clean_mesh, get_mask_use_all_frames=False)
+            if (idx % self.mesh_freq == 0) and (not (idx == 0 and self.no_mesh_on_first_frame)):
+                self.mirror_poses()
+                self.mesher.get_mesh(f"{out}/{idx:05d}_mesh.ply", self.c, self.decoders, self.keyframe_dict,
+                                     self.estimate_c2w_list, idx, self.device, show_forecast=self.mesh_coarse_level, **kw)
+            if last:
+                self.mirror_poses()
+                self.mesher.get_mesh(f"{out}/final_mesh.ply", self.c, self.decoders, self.keyframe_dict,
+                                     self.estimate_c2w_list, idx, self.device, show_forecast=self.mesh_coarse_level, **kw)
+                if os.path.exists(f"{out}/final_mesh.ply"):  # Mapper.py:649-650 (cp)
+                    shutil.copyfile(f"{out}/final_mesh.ply", f"{out}/{idx:05d}_mesh.ply")
+                if self.eval_rec:
+                    self.mesher.get_mesh(f"{out}/final_mesh_eval_rec.ply", self.c, self.decoders, self.keyframe_dict,
+                                         self.estimate_c2w_list, idx, self.device, show_forecast=False,
+                                         clean_mesh=self.clean_mesh, get_mask_use_all_frames=True)
+        return last
 
     def _next_t_rand(self, n_rays):
         return self.regulation_draws(n_rays) if self.regulation_draws is not None else None

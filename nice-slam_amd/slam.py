@@ -3,7 +3,7 @@
 Only what the path needs: camera intrinsics after resize/crop (update_cam, :113-135), the enlarged
 float64 bound (load_bound, :137-157), the hierarchical grids (grid_init, :192-250) created
 channels-last on the device, and a light state object carrying what Renderer / Tracker / Mapper
-read from `slam`.  Process orchestration (:252-307) is out of scope.
+read from `slam`.  The system on top of it is nice_slam.NICE_SLAM.
 """
 from __future__ import annotations
 

@@ -1,8 +1,9 @@
 """Tracker drop-in: camera optimisation on the HIP render path (src/Tracker.py).
 
 `optimize_cam_in_batch` keeps the reference's signature and semantics (Tracker.py:71-128).
-The frame loop's per-frame logic (Tracker.py:184-256) is `track_frame`; dataset loading,
-process synchronisation and visualisation (Tracker.py:144-183) are out of scope.
+The frame loop's per-frame logic (Tracker.py:184-256) is `track_frame`; `track` is one pass of
+Tracker.run's loop body around it (the pose lists, the strict-sync re-read of the previous pose, the
+visualiser calls), which NICE_SLAM.run schedules serially (nice_slam.py).
 
 tracking.seperate_LR (the TUM-RGBD configs; Tracker.py:202-209) takes the same fused paths as a single rate:
 the reference's two Adam groups (translation lr, quaternion lr·0.2) are one elementwise Adam over the 7-vector
@@ -154,7 +155,8 @@ class Tracker(object):
         gt_depth, gt_color = gt_depth.to(device), gt_color.to(device)
         if idx == 0 or self.gt_camera:
             return gt_c2w.clone()
-        if self.fused and self.graphs and self.generator is None and _common.select_uv is _SELECT_UV:
+        if (self.fused and self.graphs and self.generator is None and _common.select_uv is _SELECT_UV
+                and self._iter_hook is None):
             return self._track_graph(gt_color, gt_depth, pre_c2w,
                                      prev2_c2w if self.const_speed_assumption else None)
         if self.const_speed_assumption and prev2_c2w is not None:
@@ -177,14 +179,80 @@ class Tracker(object):
             camera_tensor = camera_tensor.clone().requires_grad_(True)
             optimizer = torch.optim.Adam([camera_tensor], lr=self.cam_lr)
         best, best_loss = None, np.inf
-        for _ in range(self.num_cam_iters):
+        for cam_iter in range(self.num_cam_iters):
             if self.seperate_LR:
                 camera_tensor = torch.cat([quad, T], 0)
-            loss = self.optimize_cam_in_batch(camera_tensor, gt_color, gt_depth, self.tracking_pixels, optimizer)
+            if self._iter_hook is not None:
+                self._iter_hook(cam_iter, camera_tensor)
+            loss =self.optimize_cam_in_batch(camera_tensor, gt_color, gt_depth, self.tracking_pixels, optimizer)
             if loss < best_loss:
                 best_loss, best = loss, camera_tensor.clone().detach()
         bottom = torch.tensor([[0, 0, 0, 1.0]], dtype=torch.float32, device=device)
         return torch.cat([get_camera_from_tensor(best), bottom], 0)
+
+    # -- the frame loop (Tracker.run, Tracker.py:144-258) ------------------------------------------
+    def attach_run(self, slam):
+        """What Tracker.__init__ (Tracker.py:19-69) takes from `slam` and cfg for the frame loop, and the
+        tracking visualiser.  NICE_SLAM calls it once; track_frame alone does not need it."""
+        import os
+
+        from .visualizer import Visualizer
+        cfg = self.cfg
+        self.idx = slam.idx
+        self.output = slam.output
+        self.verbose = slam.verbose
+        self.low_gpu_mem = slam.low_gpu_mem
+        self.mapping_cnt = slam.mapping_cnt
+        self.sync_method = cfg["sync_method"]
+        self.every_frame = cfg["mapping"]["every_frame"]
+        self.no_vis_on_first_frame = cfg["mapping"]["no_vis_on_first_frame"]
+        self.n_img = slam.n_img
+        self.pose_work, self.gt_pose_work = slam.pose_work, slam.gt_pose_work
+        self.visualizer = Visualizer(freq=cfg["tracking"]["vis_freq"], inside_freq=cfg["tracking"]["vis_inside_freq"],
+                                     vis_dir=os.path.join(self.output, "vis" if "Demo" in self.output else "tracking_vis"),
+                                     renderer=self.renderer, verbose=self.verbose, device=self.device)
+        self._pre_c2w = None
+
+    def track(self, idx, frame):
+        """One pass of Tracker.run's loop body (Tracker.py:152-258) for frame = (idx, color, depth, c2w) → c2w.
+
+        The pose lists are read and written through their working copies (NICE_SLAM.pose_work: on the tracking
+        device, so a tracked frame costs no host synchronisation; the CPU lists themselves when the device is
+        the CPU).  On a frame whose visualisation fires the camera loop runs eagerly with the visualiser called
+        before every iteration, as Tracker.py:228-229 has it; every other frame replays the cached graph."""
+        idx = int(idx)
+        device = self.device
+        _, gt_color, gt_depth, gt_c2w = frame
+        est = self.pose_work
+        # strict sync: the pose the mapper may have moved by BA is read again (Tracker.py:164-168); between
+        # those frames pre_c2w is the tracker's own last result (Tracker.py:254)
+        if idx > 0 and (idx % self.every_frame == 1 or self.every_frame == 1):
+            self._pre_c2w = est[idx - 1].to(device).clone()
+        if self.verbose:
+            print("Tracking Frame ", idx)
+        if idx == 0 or self.gt_camera:
+            self.update_para_from_mapping()
+            c2w = gt_c2w
+            if not self.no_vis_on_first_frame:
+                self.visualizer.vis(idx, 0, gt_depth, gt_color, c2w, self.c, self.decoders)
+        else:
+            prev2 = est[idx - 2].to(device) if (self.const_speed_assumption and idx - 2 >= 0) else None
+            vis = self.visualizer
+            if idx % vis.freq == 0:  # (the visualiser's own idx condition: it fires on some iteration)
+                self._iter_hook = lambda it, cam: vis.vis(idx, it, gt_depth, gt_color, cam, self.c, self.decoders)
+            try:
+                c2w = self.track_frame(idx, gt_color, gt_depth, gt_c2w, pre_c2w=self._pre_c2w, prev2_c2w=prev2)
+            finally:
+                self._iter_hook = None
+        est[idx] = c2w.clone()
+        self.gt_pose_work[idx] = gt_c2w.clone()
+        self._pre_c2w = c2w.clone()
+        self.idx[0] = idx
+        if self.low_gpu_mem:
+            torch.cuda.empty_cache()
+        return c2w
+
+    _iter_hook = None  # track(): called as hook(cam_iter, camera_tensor) before each camera iteration
 
     def _lr2(self):
         """iteration()'s keywords for tracking.seperate_LR (Tracker.py:202-209, 226-227): the quaternion's
@@ -208,7 +276,9 @@ class Tracker(object):
         best_loss = torch.full((), float("inf"), dtype=torch.float64, device=device)
         depth = gt_depth.float().contiguous()
         color = gt_color.float().contiguous()
-        for _ in range(self.num_cam_iters):
+        for cam_iter in range(self.num_cam_iters):
+            if self._iter_hook is not None:
+                self._iter_hook(cam_iter, cam.detach())
             pix = torch.randint(eng.n_window(), (self.tracking_pixels,), device=device, generator=self.generator)
             eng.iteration(cam, depth, color, pix, opt, best=(best_loss, best), **self._lr2())  # (+ Tracker.py:245-247)
         bottom = torch.tensor([[0, 0, 0, 1.0]], dtype=torch.float32, device=device)

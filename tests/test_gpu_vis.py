@@ -1,0 +1,120 @@
+"""The visualiser on the device: nslam_vis_panels against its numpy twin bit for bit, and Visualizer.vis — the
+file it writes, that both pose forms give the same bytes, that it fires only on its (idx, iter) condition, and
+that a call leaves the maps, the decoders, the optimiser state and the pixel-draw counters untouched."""
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN
+
+sys.path.insert(0, GOLDEN)
+import scenes  # noqa: E402
+import vis_cases  # noqa: E402
+from test_gpu_loop import loop_cfg, tiny_slam  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+P = importlib.import_module("nice-slam_amd")
+DEV = torch.device("cuda:0")
+
+
+def _random_case(H, W, seed=7):
+    rng = np.random.default_rng(seed)
+    gd = (4.0 * rng.random((H, W))).astype(np.float32)
+    gd[rng.random((H, W)) < 0.1] = 0.0
+    return (gd, rng.random((H, W, 3)).astype(np.float32), 4.5 * rng.random((H, W)) - 0.2,
+            (1.4 * rng.random((H, W, 3)) - 0.2).astype(np.float32))
+
+
+@pytest.mark.parametrize("shape", [(96, 128), (5, 7)])  # (5 x 7: W no multiple of 4 or 64, under one block)
+@pytest.mark.parametrize("case", ["edge", "zero", "random"])
+def test_panels_equal_the_twin(shape, case):
+    H, W = shape
+    gd, gc, d, c = {"edge": vis_cases.edge_case, "zero": vis_cases.zero_case, "random": _random_case}[case](H, W)
+    want = P.visualizer.vis_panels_np(gd, gc, d, c)
+    tgd = torch.from_numpy(gd).to(DEV)
+    got = P.ops.vis_panels(tgd, torch.from_numpy(gc).to(DEV), torch.from_numpy(d).to(DEV),
+                           torch.from_numpy(c).to(DEV), tgd.max())
+    assert got.dtype == torch.uint8 and tuple(got.shape) == (2 * H, 3 * W, 3)
+    got = got.cpu().numpy()
+    bad = np.argwhere((got != want).any(-1))
+    assert bad.size == 0, (case, shape, bad[:5], got[tuple(bad[0])], want[tuple(bad[0])])
+
+
+def test_panels_validate_arguments():
+    gd = torch.zeros(5, 7, device=DEV)
+    gc, d, c = torch.zeros(5, 7, 3, device=DEV), torch.zeros(5, 7, dtype=torch.float64, device=DEV), \
+        torch.zeros(5, 7, 3, device=DEV)
+    with pytest.raises(ValueError):
+        P.ops.vis_panels(gd, gc, d.float(), c, gd.max())          # depth must be float64
+    with pytest.raises(ValueError):
+        P.ops.vis_panels(gd, gc[:, :6], d, c, gd.max())           # shape
+    with pytest.raises(ValueError):
+        P.ops.vis_panels(gd, gc, d, c, torch.zeros(2, device=DEV))  # vmax is one scalar
+    assert P.ops.vis_panels(gd[:0], gc[:0], d[:0], c[:0], torch.zeros((), device=DEV)).shape == (0, 21, 3)
+
+
+@pytest.fixture(scope="module")
+def scene(tiny):
+    """The tiny scene with a mapper that has run one short call: an engine, Adam state and a draw counter
+    exist for the visualiser to leave alone."""
+    cam = scenes.TINY_CAM
+    cfg = loop_cfg(frustum=False, pixels=400)
+    slam = tiny_slam(tiny, cfg, cam)
+    b, _, cur = scenes.tiny_window()
+    depth = torch.from_numpy(scenes.box_depth(cur, cam, b, seed=40)).to(DEV)
+    color = torch.from_numpy(scenes.color_image(cam, seed=41)).to(DEV)
+    c2w = torch.from_numpy(cur).to(DEV)
+    mp = P.Mapper(cfg, None, slam)
+    mp.graphs = False
+    mp.optimize_map(3, 1.0, 0, color, depth, c2w, [], [], c2w)
+    torch.cuda.synchronize()
+    return slam, mp, depth, color, c2w
+
+
+def _tensors(obj, out):
+    if torch.is_tensor(obj):
+        out.append(obj)
+    elif isinstance(obj, dict):
+        for v in obj.values():
+            _tensors(v, out)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            _tensors(v, out)
+    return out
+
+
+def test_vis_writes_the_twins_jpeg_and_touches_nothing(scene, tmp_path):
+    slam, mp, depth, color, c2w = scene
+    v = P.Visualizer(freq=5, inside_freq=2, vis_dir=str(tmp_path / "vis"), renderer=slam.renderer, verbose=False,
+                     device="cuda:0")
+    cam = P.common.get_tensor_from_camera(c2w).to(DEV)
+    bottom = torch.tensor([[0, 0, 0, 1.0]], device=DEV)
+    c2w44 = torch.cat([P.common.get_camera_from_tensor(cam), bottom], 0)  # the same pose in both forms
+    eng = mp.engine()
+    state = _tensors(mp._fopt.state, []) + [eng.draws(mp._draw_seed).counter]
+    state += list(slam.shared_c.values()) + [p.data for p in slam.shared_decoders.parameters()]
+    assert len(_tensors(mp._fopt.state, [])) > 0
+    before = [t.clone() for t in state]
+    # off its (idx, iter) condition: a no-op
+    v.vis(5, 1, depth, color, cam, slam.shared_c, slam.shared_decoders)
+    v.vis(4, 2, depth, color, cam, slam.shared_c, slam.shared_decoders)
+    assert os.listdir(tmp_path / "vis") == []
+    v.vis(5, 2, depth, color, cam, slam.shared_c, slam.shared_decoders)
+    with open(tmp_path / "vis" / "00005_0002.jpg", "rb") as f:
+        a = f.read()
+    v.vis(torch.tensor(10), 0, depth, color.double(), c2w44, slam.shared_c, slam.shared_decoders)
+    with open(tmp_path / "vis" / "00010_0000.jpg", "rb") as f:
+        b = f.read()
+    assert a == b
+    torch.cuda.synchronize()
+    for t, t0 in zip(state, before):
+        assert torch.equal(t, t0)
+    # the file is Pillow's encoding of the twin's mosaic of render_img's own output
+    d, _, c = slam.renderer.render_img(slam.shared_c, slam.shared_decoders, c2w44, "cuda:0", stage="color", gt_depth=depth)
+    mosaic = P.visualizer.vis_panels_np(depth.cpu().numpy(), color.float().cpu().numpy(), d.cpu().numpy(), c.cpu().numpy())
+    assert mosaic.shape == (2 * 96, 3 * 128, 3)
+    assert a == P.visualizer.encode_jpeg(mosaic)
