@@ -73,6 +73,27 @@ def get_rays(H, W, fx, fy, cx, cy, c2w, device):
     return rays_o, rays_d
 
 
+def pose4(c2w):
+    """A [3,4] pose with the [0, 0, 0, 1] row under it (a [4,4] pose as it is)."""
+    if c2w.shape[0] == 4:
+        return c2w
+    return torch.cat([c2w, torch.tensor([[0, 0, 0, 1.0]], dtype=torch.float32, device=c2w.device)], 0)
+
+
+def inside_mask(rays_o, rays_d, gt_depth, bound):
+    """Mapper.py:469-481 / Tracker.py:95-100: keep rays whose AABB exit distance >= gt depth (bound on the
+    rays' device)."""
+    with torch.no_grad():
+        t = (bound.unsqueeze(0) - rays_o.detach().unsqueeze(-1)) / rays_d.detach().unsqueeze(-1)
+        return torch.min(torch.max(t, dim=2)[0], dim=1)[0] >= gt_depth
+
+
+def constant_speed_guess(pre, prev2):
+    """Tracker.py:191-198: the last motion applied once more to the last pose, both [4,4] on one device
+    (inv_ex: torch.linalg.inv without its error check, so no host sync and capturable)."""
+    return (pre @ torch.linalg.inv_ex(prev2)[0]) @ pre
+
+
 def quad2rotation(quad):
     """src/common.py:137-160 — quaternion (w,x,y,z), unnormalised (2/|q|^2), device-agnostic."""
     qr, qi, qj, qk = quad[:, 0], quad[:, 1], quad[:, 2], quad[:, 3]

@@ -28,13 +28,15 @@ serially (nice_slam.py).
 from __future__ import annotations
 
 import os
+import time
 
 import numpy as np
 import torch
 
 from . import common as _common
 from . import ops
-from .common import get_camera_from_tensor, get_samples, get_tensor_from_camera, random_select
+from .common import (get_camera_from_tensor, get_samples, get_tensor_from_camera, inside_mask, pose4,
+                     random_select)
 
 _SELECT_UV = _common.select_uv  # the product's own pixel selection (a replacement one forces eager draws)
 _STAGE_GROUPS = ("decoders", "coarse", "middle", "fine", "color")
@@ -86,6 +88,15 @@ def _grid_points(bound, val_shape, dev):
     return _POINTS[key]
 
 
+def _world_to_uvz(points, c2w, K):
+    """World points [N,3] in the pixel frame of the camera c2w ([3,4] or [4,4]) with intrinsics K, as the
+    reference projects them (Mapper.py:131-141, 196-207): float64 [N,3] = (u·z, v·z, z) with x flipped."""
+    w2c = torch.linalg.inv_ex(pose4(c2w.to(points.device).float()))[0]  # (no error check: no host sync, capturable)
+    cam = (points @ w2c[:3, :3].T + w2c[:3, 3]).double()
+    cam[:, 0] *= -1
+    return cam @ K.T
+
+
 def frustum_rows_device(c2w, val_shape, depth, bound, H, W, fx, fy, cx, cy, slot, rows, n_live, mask_ref=None):
     """frustum_mask fused with its compaction (ABI v20 nslam_frustum_rows): slot [Z*Y*X] int32, rows (>= the
     voxel count) int32 and n_live int64 [1] are written in place, as MappingEngine.bind_masks would from the
@@ -94,17 +105,19 @@ def frustum_rows_device(c2w, val_shape, depth, bound, H, W, fx, fy, cx, cy, slot
     mask_ref: optional uint8 [X*Y*Z] receiving the mask in frustum_mask's order."""
     from ._lib import check, lib, ptr, stream_ptr
     dev = depth.device
-    points = _grid_points(bound, val_shape, dev)
-    c2w = c2w.to(dev).float()
-    w2c = torch.linalg.inv_ex(c2w)[0]
-    cam = points @ w2c[:3, :3].T + w2c[:3, 3]
-    cam = cam.double()
-    cam[:, 0] *= -1
-    uvz = cam @ _intrinsics(fx, fy, cx, cy, dev).T
-    d = points - c2w[:3, 3]
-    near = ((d * d).sum(1) < 0.5 * 0.5).to(torch.uint8)
     nz, ny, nx = (int(v) for v in val_shape)
     n = nx * ny * nz
+    for name, t in (("slot", slot), ("rows", rows)):  # (the kernels write n entries of each)
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < n:
+            raise ValueError(f"frustum_rows_device: {name} must be contiguous int32 with at least {n} entries, got "
+                             f"{t.dtype} {tuple(t.shape)}")
+    if n_live.dtype != torch.int64 or tuple(n_live.shape) != (1,):
+        raise ValueError(f"frustum_rows_device: n_live must be int64 [1], got {n_live.dtype} {tuple(n_live.shape)}")
+    points = _grid_points(bound, val_shape, dev)
+    c2w = c2w.to(dev).float()
+    uvz = _world_to_uvz(points, c2w, _intrinsics(fx, fy, cx, cy, dev))
+    d = points - c2w[:3, 3]
+    near = ((d * d).sum(1) < 0.5 * 0.5).to(torch.uint8)
     wsb = lib().nslam_frustum_rows_workspace_size(n)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     dep = depth.float().contiguous()
@@ -121,20 +134,9 @@ def frustum_mask(c2w, key, val_shape, depth, bound, H, W, fx, fy, cx, cy):
     nz, ny, nx = val_shape[0], val_shape[1], val_shape[2]
     if key == "grid_coarse":
         return torch.ones(nx, ny, nz, dtype=torch.bool, device=dev)
-    b = bound
-    X, Y, Z = torch.meshgrid(torch.linspace(float(b[0][0]), float(b[0][1]), nx, device=dev),
-                             torch.linspace(float(b[1][0]), float(b[1][1]), ny, device=dev),
-                             torch.linspace(float(b[2][0]), float(b[2][1]), nz, device=dev), indexing="ij")
-    points = torch.stack([X, Y, Z], dim=-1).reshape(-1, 3)
+    points = _grid_points(bound, val_shape, dev)
     c2w = c2w.to(dev).float()
-    if c2w.shape[0] == 3:
-        c2w = torch.cat([c2w, torch.tensor([[0, 0, 0, 1.0]], device=dev)], 0)
-    w2c = torch.linalg.inv_ex(c2w)[0]  # (torch.linalg.inv without its error check: no host sync, capturable)
-    cam = points @ w2c[:3, :3].T + w2c[:3, 3]
-    cam = cam.double()
-    cam[:, 0] *= -1
-    K = _intrinsics(fx, fy, cx, cy, dev)
-    uvz = cam @ K.T
+    uvz = _world_to_uvz(points, c2w, _intrinsics(fx, fy, cx, cy, dev))
     z = uvz[:, 2] + 1e-5
     uv = (uvz[:, :2] / z[:, None]).float()
     depths = _remap_bilinear(depth.float(), uv[:, 0], uv[:, 1])
@@ -145,6 +147,75 @@ def frustum_mask(c2w, key, val_shape, depth, bound, H, W, fx, fy, cx, cy):
     d = points - ray_o
     mask = mask | ((d * d).sum(1) < 0.5 * 0.5)
     return mask.reshape(nx, ny, nz)
+
+
+class _Window(object):
+    """One fused optimize_map call's window: its frames copied into the mapper's persistent slots (the oldest
+    frame, fixed under BA, first; then the others in optimize_frame order) and, with BA, the camera buffers.
+    F frames of n_per pixels each; slots c0.. hold the ncam optimised cameras; poses [F,3,4] as copied in;
+    ar: the pixel index table of eager select_uv draws (None: the gather kernel draws)."""
+
+    def __init__(self, mapper, optimize_frame, oldest_frame, keyframe_dict, cur_gt_depth, cur_gt_color, cur_c2w,
+                 device_draws):
+        dev = mapper.device
+        self.optimize_frame = optimize_frame
+        F = self.F = len(optimize_frame)
+        self.n_per = mapper.mapping_pixels // F
+        fixed = mapper.BA and oldest_frame is not None
+        self.order = list(optimize_frame)
+        if fixed:
+            self.order.remove(oldest_frame)
+            self.order.insert(0, oldest_frame)
+        depth_s, color_s, self.c2w_s = mapper._window_slots(F)
+        poses = []
+        for s, fr in enumerate(self.order):
+            if fr == -1:
+                d, c, m = cur_gt_depth, cur_gt_color, cur_c2w
+            else:
+                d, c = mapper._frame_images(keyframe_dict[fr])
+                m = keyframe_dict[fr]["est_c2w"].to(dev).float()
+            depth_s[s].copy_(d)
+            color_s[s].copy_(c)
+            poses.append(m[:3])
+        self.poses = torch.stack(poses)
+        self.restore_poses()
+        self.frames = [(depth_s[s], color_s[s], self.c2w_s[s]) for s in range(F)]
+        c0 = self.c0 = 1 if fixed else 0
+        self.ncam = (F - c0) if mapper.BA else 0
+        if self.ncam:  # the 7-vectors of the optimised frames (Mapper.py:349-363)
+            self.cams, self.cgrad, self.cws, self.ctk, self.copt = mapper._cam_state(self.ncam)
+            self.copt.init_state()
+            # the optimised frames are gathered from their 7-vectors: the gather forms each pose
+            # (get_camera_from_tensor) and writes it to the frame's slot for the camera gradient (ABI v21)
+            self.frames[c0:] = [(depth_s[s], color_s[s], self.c2w_s[s], self.cams[s - c0]) for s in range(c0, F)]
+        self.ar = None if device_draws else torch.arange(mapper.H * mapper.W, device=dev)
+
+    def restore_poses(self):
+        self.c2w_s[:self.F, :3].copy_(self.poses)
+
+    def cams_init(self):
+        """The BA cameras from the slots' poses (get_tensor_from_camera of each, one launch), a fresh Adam."""
+        ops.cam_vector_batch(self.c2w_s[self.c0:self.F], self.cams)
+        self.copt.reset_state()
+
+    def post_bwd(self, gps, ro, rd, z):
+        """BA: camera gradients of every optimised frame, then their Adam step."""
+        c0, n_per = self.c0, self.n_per
+        ops.cam_grad_batch(self.cams, self.c2w_s[c0:self.F], [(c0 + k) * n_per for k in range(self.ncam)], n_per, gps,
+                           z, rd, self.cgrad, self.cws, self.ctk)
+        self.copt.step(grads={self.cams: self.cgrad})
+
+    def write_back(self, keyframe_dict, cur_c2w):
+        """Mapper.py:521-540: the optimised poses into keyframe_dict; returns the current frame's."""
+        out = torch.zeros(self.ncam, 4, 4, dtype=torch.float32, device=self.cams.device)
+        out[:, 3, 3] = 1.0
+        ops.cam_pose_batch(self.cams, out)
+        for k, fr in enumerate(self.order[self.c0:]):
+            if fr == -1:
+                cur_c2w = out[k]
+            else:
+                keyframe_dict[fr]["est_c2w"] = out[k]
+        return cur_c2w
 
 
 class Mapper(object):
@@ -228,10 +299,7 @@ class Mapper(object):
         K = _intrinsics(fx, fy, cx, cy, dev)
         counts = []
         for pose in poses:
-            w2c = torch.linalg.inv_ex(pose.to(dev).float())[0]
-            cam = (verts @ w2c[:3, :3].T + w2c[:3, 3]).double()
-            cam[:, 0] *= -1
-            uvz = cam @ K.T
+            uvz = _world_to_uvz(verts, pose, K)
             zz = uvz[:, 2] + 1e-5
             uv = (uvz[:, :2] / zz[:, None]).float()
             edge = 20
@@ -264,31 +332,31 @@ class Mapper(object):
         """Mapping iterations (Mapper.py:230-540); returns the BA-updated cur_c2w or None."""
         self.calls += 1
         if not self.nice:  # iMAP*: the autograd loop only (no fused engine, no graph capture)
-            return self._optimize_map_imap(num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
-                                           keyframe_dict, keyframe_list, cur_c2w)
-        if self.fused:
-            return self._optimize_map_fused(num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
-                                            keyframe_dict, keyframe_list, cur_c2w)
-        return self._optimize_map_autograd(num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
-                                           keyframe_dict, keyframe_list, cur_c2w)
+            impl = self._optimize_map_imap
+        else:
+            impl = self._optimize_map_fused if self.fused else self._optimize_map_autograd
+        return impl(num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w, keyframe_dict,
+                    keyframe_list, cur_c2w)
 
     # ------------------------------------------------------------------------------------------
-    def _select_window(self, keyframe_dict, keyframe_list, cur_gt_color, cur_gt_depth, cur_c2w):
-        """optimize_frame (keyframe ids, -1 = the current frame) and the oldest one (Mapper.py:256-272,
-        346-349)."""
+    def _select_keyframes(self, keyframe_dict, cur_gt_color, cur_gt_depth, cur_c2w):
+        """The keyframes selected for the window besides the last one (Mapper.py:256-266)."""
         if len(keyframe_dict) == 0:
-            optimize_frame = []
-        elif self.keyframe_selection_method == "global":
-            optimize_frame = random_select(len(self.keyframe_dict) - 1, self.mapping_window_size - 2)
-        else:
-            optimize_frame = self.keyframe_selection_overlap(cur_gt_color, cur_gt_depth, cur_c2w, keyframe_dict[:-1],
-                                                             self.mapping_window_size - 2)
-        oldest_frame = None
+            return []
+        if self.keyframe_selection_method == "global":
+            return random_select(len(self.keyframe_dict) - 1, self.mapping_window_size - 2)
+        return self.keyframe_selection_overlap(cur_gt_color, cur_gt_depth, cur_c2w, keyframe_dict[:-1],
+                                               self.mapping_window_size - 2)
+
+    @staticmethod
+    def _window_of(selected, keyframe_list):
+        """optimize_frame (the selection, the last keyframe, -1 = the current frame) and the oldest keyframe
+        in it (Mapper.py:268-272, 346-349)."""
+        optimize_frame, oldest_frame = list(selected), None
         if len(keyframe_list) > 0:
-            optimize_frame = optimize_frame + [len(keyframe_list) - 1]
+            optimize_frame.append(len(keyframe_list) - 1)
             oldest_frame = min(optimize_frame)
-        optimize_frame += [-1]
-        return optimize_frame, oldest_frame
+        return optimize_frame + [-1], oldest_frame
 
     def _stage_of(self, joint_iter, num_joint_iters):
         """Mapper.py:403-411."""
@@ -299,6 +367,17 @@ class Mapper(object):
         if joint_iter <= int(num_joint_iters * self.fine_iter_ratio):
             return "fine"
         return "color"
+
+    def _stage_runs(self, num_joint_iters):
+        """A call's schedule as runs of one stage: [(stage, iterations), ...] (Mapper.py:403-421)."""
+        runs = []
+        for it in range(num_joint_iters):
+            stg = self._stage_of(it, num_joint_iters)
+            if runs and runs[-1][0] == stg:
+                runs[-1][1] += 1
+            else:
+                runs.append([stg, 1])
+        return [tuple(r) for r in runs]
 
     def _grid_keys(self):
         return ["grid_coarse"] if self.coarse_mapper else [k for k in ("grid_middle", "grid_fine", "grid_color")
@@ -411,23 +490,115 @@ class Mapper(object):
             self._graphs = {k: v for k, v in self._graphs.items() if k[0] != "setup"}  # (bound to the old buffers)
         return st
 
+    # -- optimize_map on the fused engine (see the module docstring) -------------------------------
+    @staticmethod
+    def _mark(tm, name):
+        """Host time and a HIP event on the caller's stream at a phase boundary of a timed call."""
+        if tm is not None:
+            tm[name] = time.perf_counter()
+            tm["ev"][name] = torch.cuda.Event(enable_timing=True)
+            tm["ev"][name].record()
+
+    def _fused_setup(self, eng, use_graphs, overlap_here, cur_gt_color, cur_gt_depth, cur_c2w, keyframe_dict):
+        """What a call enqueues before its keyframe selection: the frustum selection (Mapper.py:314-333) bound
+        on the device, a fresh Adam (Mapper.py:365-389: zero moments and step counts) and, when overlap_here,
+        the overlap counts of keyframe_dict[:-1] — with graphs as one captured graph per keyframe count over
+        persistent inputs.  Returns (optimiser, counts, samples)."""
+        if not use_graphs:
+            self._bind_frustum(eng, cur_c2w, cur_gt_depth)
+            opt = self._optimizer(eng)
+            opt.reset_state()
+            return opt, None, 0
+        dev = self.device
+        kfs = keyframe_dict[:-1] if overlap_here else []
+        st = self._setup_inputs(len(kfs))
+        st["depth"].copy_(cur_gt_depth)
+        st["color"].copy_(cur_gt_color)
+        st["c2w"][:cur_c2w.shape[0]].copy_(cur_c2w)
+        if kfs:
+            st["poses"][:len(kfs)].copy_(torch.stack([kf["est_c2w"].to(dev).float()[:4] for kf in kfs]))
+
+        def setup():
+            self._bind_frustum(eng, st["c2w"], st["depth"])
+            o = self._optimizer(eng)
+            o.init_state()
+            o.reset_state()
+            if kfs:
+                return self._overlap_counts(st["color"], st["depth"], st["c2w"],
+                                            [st["poses"][i] for i in range(len(kfs))])
+            return None, 0
+
+        key = ("setup", len(kfs))
+        if key not in self._graphs:
+            setup()  # eager warm-up: first-time allocations (engine capacity buffers, Adam state, caches)
+            g = torch.cuda.CUDAGraph()
+            with ops.capture(g):
+                out = setup()
+            self._graphs[key] = (g, out)
+        g, (counts, n_samp) = self._graphs[key]
+        g.replay()
+        return self._optimizer(eng), counts, n_samp
+
+    def _fused_iteration(self, eng, opt, win, stage, record=None):
+        """One mapping iteration on the engine over the window `win`; record(ray_loss) when given."""
+        H, W, n_per = self.H, self.W, win.n_per
+        pix = None
+        if win.ar is not None:  # select_uv per frame, in optimize_frame order (Mapper.py:437-467)
+            ar = win.ar
+            pix = torch.empty(win.F * n_per, dtype=torch.int64, device=self.device)
+            for fr in win.optimize_frame:
+                s = win.order.index(fr)
+                pix[s * n_per:(s + 1) * n_per] = _common.select_uv(ar, ar, n_per, ar, ar.view(-1, 1).expand(-1, 3),
+                                                                   device=self.device, generator=self.generator)[0]
+        # device draws: the next iteration's gather + sampler run beside this one's render and backward
+        # (engine prefetch); every run of one stage starts with its own batch (eng._pre reset), so a
+        # captured run holds its whole prefetch chain.  With BA the poses the rays come from move only in
+        # the colour stage (the cameras' lr is 0 before it, Mapper.py:420-421: their Adam state advances,
+        # the 7-vectors do not), so only colour-stage BA iterations draw their rays serially.
+        prefetch = win.ar is None and (not win.ncam or stage != "color")
+        ray_loss, _ = eng.iteration(stage, win.frames, pix, n_per, (H, W), (self.fx, self.fy, self.cx, self.cy), opt,
+                                    trainable_decoders=self._trainable(), use_gt_in_sampler=not self.coarse_mapper,
+                                    seed=self._draw_seed, post_bwd=win.post_bwd if win.ncam else None,
+                                    prefetch=prefetch)
+        if record is not None:
+            record(ray_loss)
+
+    def _set_stage_lr(self, opt, win, stage, lr_factor, zero=False):
+        """The stage's learning rates (Mapper.py:413-421), or all zero."""
+        st = self.cfg["mapping"]["stage"][stage]
+        for gi, name in enumerate(_STAGE_GROUPS):
+            opt.param_groups[gi]["lr"] = 0.0 if zero else st[name + "_lr"] * lr_factor
+        if win.ncam:
+            win.copt.param_groups[0]["lr"] = self.BA_cam_lr if (stage == "color" and not zero) else 0.0
+
+    def _capture_stage(self, eng, opt, win, stage, n, lr_factor, first):
+        """n iterations of one stage as a hipGraph → (graph, its losses or None).  Before it one zero-lr eager
+        iteration (the maps do not move; lazily made streams, events, tickets and draw counters exist before
+        capture); the capture itself runs nothing.  first: the graph also sets the BA cameras up."""
+        if win.ncam:
+            win.cams_init()
+        self._set_stage_lr(opt, win, stage, lr_factor, zero=True)
+        eng._pre = None
+        self._fused_iteration(eng, opt, win, stage)
+        self._set_stage_lr(opt, win, stage, lr_factor)
+        losses = None
+        if self.loss_history is not None:
+            losses = torch.zeros(n, dtype=torch.float64, device=self.device)
+        g = torch.cuda.CUDAGraph()
+        eng._pre = None
+        with ops.capture(g):
+            if first:
+                win.cams_init()
+            for i in range(n):
+                self._fused_iteration(eng, opt, win, stage,
+                                      None if losses is None else (lambda rl, i=i: losses[i].copy_(rl.sum())))
+        return g, losses
+
     def _optimize_map_fused(self, num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
                             keyframe_dict, keyframe_list, cur_c2w):
-        """optimize_map on the fused engine (see the module docstring)."""
+        """optimize_map on the fused engine, in the numbered steps below (see the module docstring)."""
         dev = self.device
-        H, W = self.H, self.W
-        tm = None
-        if self.timing is not None:
-            import time
-            tm = {"t0": time.perf_counter(), "clock": time.perf_counter, "ev": {}}
-
-        def mark(name):  # host time and a HIP event on the caller's stream at a phase boundary
-            if tm is not None:
-                tm[name] = tm["clock"]()
-                e = torch.cuda.Event(enable_timing=True)
-                e.record()
-                tm["ev"][name] = e
-
+        tm = {"t0": time.perf_counter(), "ev": {}} if self.timing is not None else None
         cur_gt_depth = cur_gt_depth.to(dev).float()
         cur_gt_color = cur_gt_color.to(dev).float()
         cur_c2w = cur_c2w.to(dev).float()
@@ -436,244 +607,143 @@ class Mapper(object):
             d.repack()
         device_draws = _common.select_uv is _SELECT_UV and self.generator is None
         use_graphs = self.graphs and device_draws and self._iter_hook is None  # (a hooked call runs eagerly)
-        # Everything that does not depend on the keyframe selection is enqueued first: the selection reads
+        # 1. Everything that does not depend on the keyframe selection is enqueued first: the selection reads
         # its overlap scores back to the host (the reference's numpy ranking), and what is queued before
-        # that read overlaps the previous call's iterations still running on the device: this call's
-        # frustum selection (Mapper.py:314-333) bound on the device, a fresh Adam (Mapper.py:365-389: zero
-        # moments and step counts) and, with graphs, the overlap counts — one captured graph per keyframe count.
+        # that read overlaps the previous call's iterations still running on the device.
         overlap_here = (use_graphs and self.keyframe_selection_method == "overlap" and len(keyframe_dict) > 1
                         and "keyframe_selection_overlap" not in self.__dict__)
-        if use_graphs:
-            kfs = keyframe_dict[:-1] if overlap_here else []
-            st = self._setup_inputs(len(kfs))
-            st["depth"].copy_(cur_gt_depth)
-            st["color"].copy_(cur_gt_color)
-            st["c2w"][:cur_c2w.shape[0]].copy_(cur_c2w)
-            if kfs:
-                st["poses"][:len(kfs)].copy_(torch.stack([kf["est_c2w"].to(dev).float()[:4] for kf in kfs]))
-
-            def setup():
-                self._bind_frustum(eng, st["c2w"], st["depth"])
-                o = self._optimizer(eng)
-                o.init_state()
-                o.reset_state()
-                if kfs:
-                    cnt, n = self._overlap_counts(st["color"], st["depth"], st["c2w"],
-                                                  [st["poses"][i] for i in range(len(kfs))])
-                    return cnt, n
-                return None, 0
-
-            key = ("setup", len(kfs))
-            if key not in self._graphs:
-                setup()  # eager warm-up: first-time allocations (engine capacity buffers, Adam state, caches)
-                g = torch.cuda.CUDAGraph()
-                with ops.capture(g):
-                    out = setup()
-                self._graphs[key] = (g, out)
-            g, (counts, n_samp) = self._graphs[key]
-            g.replay()
-            opt = self._optimizer(eng)
+        opt, counts, n_samp = self._fused_setup(eng, use_graphs, overlap_here, cur_gt_color, cur_gt_depth, cur_c2w,
+                                                keyframe_dict)
+        self._mark(tm, "masks")
+        # 2. the window: from the captured overlap counts (one read-back; Mapper.py:256-272) or selected here
+        if overlap_here:
+            selected = self._rank_keyframes([int(c) / n_samp for c in counts.cpu()], self.mapping_window_size - 2)
         else:
-            self._bind_frustum(eng, cur_c2w, cur_gt_depth)
-            opt = self._optimizer(eng)
-            opt.reset_state()
-        mark("masks")
-        if overlap_here:  # the window from the captured overlap counts (one read-back; Mapper.py:256-272)
-            scores = [int(c) / n_samp for c in counts.cpu()]
-            optimize_frame = self._rank_keyframes(scores, self.mapping_window_size - 2)
-            oldest_frame = None
-            if len(keyframe_list) > 0:
-                optimize_frame = optimize_frame + [len(keyframe_list) - 1]
-                oldest_frame = min(optimize_frame)
-            optimize_frame += [-1]
-        else:
-            optimize_frame, oldest_frame = self._select_window(keyframe_dict, keyframe_list, cur_gt_color,
-                                                               cur_gt_depth, cur_c2w)
-        mark("selected")
+            selected = self._select_keyframes(keyframe_dict, cur_gt_color, cur_gt_depth, cur_c2w)
+        optimize_frame, oldest_frame = self._window_of(selected, keyframe_list)
+        self._mark(tm, "selected")
         self._record_selected(idx, optimize_frame, keyframe_dict, keyframe_list, gt_cur_c2w, cur_c2w)
-        F = len(optimize_frame)
-        n_per = self.mapping_pixels // F
-        # window slots: the oldest frame (fixed under BA) first, then the others in optimize_frame order
-        order = list(optimize_frame)
-        if self.BA and oldest_frame is not None:
-            order.remove(oldest_frame)
-            order.insert(0, oldest_frame)
-        depth_s, color_s, c2w_s = self._window_slots(F)
-        poses = []
-        for s, fr in enumerate(order):
-            if fr == -1:
-                d, c, m = cur_gt_depth, cur_gt_color, cur_c2w
-            else:
-                d, c = self._frame_images(keyframe_dict[fr])
-                m = keyframe_dict[fr]["est_c2w"].to(dev).float()
-            depth_s[s].copy_(d)
-            color_s[s].copy_(c)
-            poses.append(m[:3])
-        poses = torch.stack(poses)
-        c2w_s[:F, :3].copy_(poses)
-        frames = [(depth_s[s], color_s[s], c2w_s[s]) for s in range(F)]
-        c0 = 1 if (self.BA and oldest_frame is not None) else 0
-        ncam = (F - c0) if self.BA else 0
-        cam = None
-        if ncam:  # the 7-vectors of the optimised frames (Mapper.py:349-363)
-            cams, cgrad, cws, ctk, copt = cam = self._cam_state(ncam)
-            copt.init_state()
-
-            def cams_init():  # (captured with the first stage's graph below)
-                ops.cam_vector_batch(c2w_s[c0:F], cams)  # get_tensor_from_camera of each, one launch
-                copt.reset_state()
-
-            # the optimised frames are gathered from their 7-vectors: the gather forms each pose
-            # (get_camera_from_tensor) and writes it to the frame's slot for the camera gradient (ABI v21)
-            frames[c0:] = [(depth_s[s], color_s[s], c2w_s[s], cams[s - c0]) for s in range(c0, F)]
-
-        def post_bwd(gps, ro, rd, z):  # BA: camera gradients of every optimised frame, then their Adam step
-            ops.cam_grad_batch(cams, c2w_s[c0:F], [(c0 + k) * n_per for k in range(ncam)], n_per, gps, z, rd, cgrad,
-                               cws, ctk)
-            copt.step(grads={cams: cgrad})
-
-        intr = (self.fx, self.fy, self.cx, self.cy)
-        tdec = self._trainable()
-        ar = torch.arange(H * W, device=dev) if not device_draws else None
-        # device draws: the next iteration's gather + sampler run beside this one's render and backward
-        # (engine prefetch); every run of one stage starts with its own batch (eng._pre reset), so a
-        # captured run holds its whole prefetch chain.  With BA the poses the rays come from move only in
-        # the colour stage (the cameras' lr is 0 before it, Mapper.py:420-421: their Adam state advances,
-        # the 7-vectors do not), so only colour-stage BA iterations draw their rays serially.
-        def prefetch_for(stage):
-            return device_draws and (not ncam or stage != "color")
-
-        def iteration(stage, record=None):
-            pix = None
-            if not device_draws:  # select_uv per frame, in optimize_frame order (Mapper.py:437-467)
-                pix = torch.empty(F * n_per, dtype=torch.int64, device=dev)
-                for fr in optimize_frame:
-                    s = order.index(fr)
-                    pix[s * n_per:(s + 1) * n_per] = _common.select_uv(ar, ar, n_per, ar, ar.view(-1, 1).expand(-1, 3),
-                                                                       device=dev, generator=self.generator)[0]
-            ray_loss, _ = eng.iteration(stage, frames, pix, n_per, (H, W), intr, opt, trainable_decoders=tdec,
-                                        use_gt_in_sampler=not self.coarse_mapper, seed=self._draw_seed,
-                                        post_bwd=post_bwd if ncam else None, prefetch=prefetch_for(stage))
-            if record is not None:
-                record(ray_loss)
-
-        def set_lr(stage, zero=False):
-            st_ = self.cfg["mapping"]["stage"][stage]
-            for gi, name in enumerate(_STAGE_GROUPS):
-                opt.param_groups[gi]["lr"] = 0.0 if zero else st_[name + "_lr"] * lr_factor
-            if cam is not None:
-                copt.param_groups[0]["lr"] = self.BA_cam_lr if (stage == "color" and not zero) else 0.0
-
-        # the call's schedule as runs of one stage (Mapper.py:403-421)
-        runs = []
-        for it in range(num_joint_iters):
-            stg = self._stage_of(it, num_joint_iters)
-            if runs and runs[-1][0] == stg:
-                runs[-1][1] += 1
-            else:
-                runs.append([stg, 1])
+        # 3. its frames in the persistent slots, and the BA cameras
+        win = _Window(self, optimize_frame, oldest_frame, keyframe_dict, cur_gt_depth, cur_gt_color, cur_c2w,
+                      device_draws)
+        # 4. the schedule; 5. with graphs, each run's graph (cached by everything it was captured for)
+        runs = self._stage_runs(num_joint_iters)
         hist = self.loss_history
-        plan = []
-        warmed = False
         if use_graphs:
-            # the warm-up iterations below draw pixels too: the draw stream is rewound afterwards, so a call
-            # draws the same pixels whether its graphs were cached or just captured (and as the eager path)
+            # the warm-up iterations of a capture draw pixels too: the draw stream is rewound afterwards, so a
+            # call draws the same pixels whether its graphs were cached or just captured (and as the eager path)
             ctr = eng.draws(self._draw_seed).counter
             ctr0 = ctr.clone()
+            plan, warmed = [], False
             for ri, (stg, n) in enumerate(runs):
-                first = ri == 0 and ncam > 0  # the first run's graph also sets the BA cameras up
-                key = ("stage", stg, n, F, n_per, c0, ncam, float(lr_factor), hist is not None, tdec, first)
+                first = ri == 0 and win.ncam > 0
+                key = ("stage", stg, n, win.F, win.n_per, win.c0, win.ncam, float(lr_factor), hist is not None,
+                       self._trainable(), first)
                 if key not in self._graphs:
-                    # one zero-lr eager iteration (the maps do not move; lazily made streams, events, tickets
-                    # and draw counters exist before capture), then the capture itself (nothing runs)
-                    if ncam:
-                        cams_init()
-                    set_lr(stg, zero=True)
-                    eng._pre = None
-                    iteration(stg)
+                    self._graphs[key] = self._capture_stage(eng, opt, win, stg, n, lr_factor, first)
                     warmed = True
-                    set_lr(stg)
-                    losses = torch.zeros(n, dtype=torch.float64, device=dev) if hist is not None else None
-                    g = torch.cuda.CUDAGraph()
-                    eng._pre = None
-                    with ops.capture(g):
-                        if first:
-                            cams_init()
-                        for i in range(n):
-                            iteration(stg, None if losses is None else (lambda rl, i=i: losses[i].copy_(rl.sum())))
-                    self._graphs[key] = (g, losses)
-                plan.append((stg, n, self._graphs[key]))
+                plan.append((stg, self._graphs[key]))
             ctr.copy_(ctr0)
-        if warmed:  # (the warm-up steps moved the Adam state and rewrote the BA cameras' poses)
-            opt.reset_state()
-            c2w_s[:F, :3].copy_(poses)
-        mark("window")
+            if warmed:  # (the warm-up steps moved the Adam state and rewrote the BA cameras' poses)
+                opt.reset_state()
+                win.restore_poses()
+        self._mark(tm, "window")
+        # 6. the iterations: replayed, or eagerly with the hook before each (Mapper.py:426-428)
         if use_graphs:
-            for stg, n, (g, losses) in plan:
+            for stg, (g, losses) in plan:
                 self.stage = stg
                 g.replay()
                 if hist is not None:
                     hist.extend(losses.clone().unbind())
         else:
-            if ncam:
-                cams_init()
+            if win.ncam:
+                win.cams_init()
             joint_iter = 0
             for stg, n in runs:
                 self.stage = stg
-                set_lr(stg)
+                self._set_stage_lr(opt, win, stg, lr_factor)
                 eng._pre = None
                 for _ in range(n):
-                    if self._iter_hook is not None:  # (Mapper.py:426-428: before the iteration's work)
+                    if self._iter_hook is not None:
                         self._iter_hook(joint_iter)
                     joint_iter += 1
-                    iteration(stg, None if hist is None else (lambda rl: hist.append(rl.sum())))
-        mark("iterations")
+                    self._fused_iteration(eng, opt, win, stg,
+                                          None if hist is None else (lambda rl: hist.append(rl.sum())))
+        self._mark(tm, "iterations")
         if tm is not None:
             self.timing.append(tm)
-        if not ncam:
-            return None
-        # BA write-back (Mapper.py:521-540): the optimised poses of the keyframes and the current frame
-        out = torch.zeros(ncam, 4, 4, dtype=torch.float32, device=dev)
-        out[:, 3, 3] = 1.0
-        ops.cam_pose_batch(cams, out)
-        for k in range(ncam):
-            fr = order[c0 + k]
-            if fr == -1:
-                cur_c2w = out[k]
+        # 7. BA write-back (Mapper.py:521-540)
+        return win.write_back(keyframe_dict, cur_c2w) if win.ncam else None
+
+    # -- optimize_map under autograd: the NICE drop-in and iMAP* -----------------------------------
+    def _autograd_window(self, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w, keyframe_dict, keyframe_list, cur_c2w):
+        """The current frame on the device and the call's window (Mapper.py:240-287)."""
+        cur = (cur_gt_depth.to(self.device), cur_gt_color.to(self.device).float(), cur_c2w.to(self.device))
+        optimize_frame, oldest_frame = self._window_of(self._select_keyframes(keyframe_dict, cur[1], cur[0], cur[2]),
+                                                       keyframe_list)
+        self._record_selected(idx, optimize_frame, keyframe_dict, keyframe_list, gt_cur_c2w, cur[2])
+        return cur, optimize_frame, oldest_frame
+
+    def _ba_cameras(self, optimize_frame, oldest_frame, keyframe_dict, cur_c2w):
+        """The 7-vector leaves of the window's cameras but the oldest (Mapper.py:349-363); none without BA."""
+        cam_tensors = []
+        if self.BA:
+            for frame in optimize_frame:
+                if frame != oldest_frame:
+                    c2w = keyframe_dict[frame]["est_c2w"] if frame != -1 else cur_c2w
+                    cam_tensors.append(get_tensor_from_camera(c2w).to(self.device).requires_grad_(True))
+        return cam_tensors
+
+    def _window_rays(self, optimize_frame, oldest_frame, keyframe_dict, cam_tensors, cur, pixs_per_image):
+        """An iteration's ray batch (Mapper.py:437-467): pixs_per_image draws per frame in optimize_frame order,
+        through the BA leaves where a frame has one.  cur = (depth, colour, c2w) of the current frame."""
+        H, W, fx, fy, cx, cy = self.H, self.W, self.fx, self.fy, self.cx, self.cy
+        device = self.device
+        batch = []
+        cam_id = 0
+        for frame in optimize_frame:
+            if frame != -1:
+                gt_depth, gt_color = self._frame_images(keyframe_dict[frame])
+                if self.BA and frame != oldest_frame:
+                    c2w = get_camera_from_tensor(cam_tensors[cam_id])
+                    cam_id += 1
+                else:
+                    c2w = keyframe_dict[frame]["est_c2w"].to(device)
             else:
-                keyframe_dict[fr]["est_c2w"] = out[k]
+                gt_depth, gt_color = cur[0], cur[1]
+                c2w = get_camera_from_tensor(cam_tensors[cam_id]) if self.BA else cur[2]
+            batch.append([t.float() for t in get_samples(0, H, 0, W, pixs_per_image, H, W, fx, fy, cx, cy, c2w,
+                                                         gt_depth, gt_color, device, generator=self.generator)])
+        return [torch.cat(ts) for ts in zip(*batch)]  # rays_o, rays_d, gt_depth, gt_color
+
+    def _ba_write_back(self, optimize_frame, oldest_frame, keyframe_dict, cam_tensors, cur_c2w):
+        """Mapper.py:521-540: the optimised poses into keyframe_dict; returns the current frame's (None without BA)."""
+        if not self.BA:
+            return None
+        cam_id = 0
+        for frame in optimize_frame:
+            if frame != -1:
+                if frame != oldest_frame:
+                    c2w = get_camera_from_tensor(cam_tensors[cam_id].detach())
+                    keyframe_dict[frame]["est_c2w"] = pose4(c2w).clone()
+                    cam_id += 1
+            else:
+                cur_c2w = pose4(get_camera_from_tensor(cam_tensors[-1].detach())).clone()
         return cur_c2w
 
     def _optimize_map_autograd(self, num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
                                keyframe_dict, keyframe_list, cur_c2w):
         """The autograd drop-in of optimize_map (Mapper.py:230-540 line for line, HIP ops under autograd)."""
-        H, W, fx, fy, cx, cy = self.H, self.W, self.fx, self.fy, self.cx, self.cy
         c, cfg, device = self.c, self.cfg, self.device
-        bottom = torch.tensor([[0, 0, 0, 1.0]], dtype=torch.float32, device=device)
-        cur_gt_depth = cur_gt_depth.to(device)
-        cur_gt_color = cur_gt_color.to(device).float()
-        cur_c2w = cur_c2w.to(device)
-
-        if len(keyframe_dict) == 0:
-            optimize_frame = []
-        elif self.keyframe_selection_method == "global":
-            optimize_frame = random_select(len(self.keyframe_dict) - 1, self.mapping_window_size - 2)
-        else:
-            optimize_frame = self.keyframe_selection_overlap(cur_gt_color, cur_gt_depth, cur_c2w, keyframe_dict[:-1],
-                                                             self.mapping_window_size - 2)
-        oldest_frame = None
-        if len(keyframe_list) > 0:
-            optimize_frame = optimize_frame + [len(keyframe_list) - 1]
-            oldest_frame = min(optimize_frame)
-        optimize_frame += [-1]
-        self._record_selected(idx, optimize_frame, keyframe_dict, keyframe_list, gt_cur_c2w, cur_c2w)
+        cur, optimize_frame, oldest_frame = self._autograd_window(idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
+                                                                  keyframe_dict, keyframe_list, cur_c2w)
         pixs_per_image = self.mapping_pixels // len(optimize_frame)
 
-        groups ={"decoders": [], "coarse": [], "middle": [], "fine": [], "color": []}
+        groups = {name: [] for name in _STAGE_GROUPS}
         masked = {}
         for key, val in c.items():
             if self.frustum_feature_selection:
-                mask = self.get_mask_from_c2w(cur_c2w, key, val.shape[2:], cur_gt_depth)
+                mask = self.get_mask_from_c2w(cur[2], key, val.shape[2:], cur[0])
                 mask = mask.permute(2, 1, 0)[None, None].expand(1, val.shape[1], -1, -1, -1)
                 vg = val.detach()[mask].clone().requires_grad_(True)
                 masked[key] = (vg, mask)
@@ -693,15 +763,8 @@ class Mapper(object):
         for p in self.decoders.parameters():
             p.requires_grad_(id(p) in ids)
 
-        cam_tensors = []
-        if self.BA:
-            for frame in optimize_frame:
-                if frame != oldest_frame:
-                    c2w = keyframe_dict[frame]["est_c2w"] if frame != -1 else cur_c2w
-                    cam_tensors.append(get_tensor_from_camera(c2w).to(device).requires_grad_(True))
-        pg = [{"params": groups["decoders"], "lr": 0}, {"params": groups["coarse"], "lr": 0},
-              {"params": groups["middle"], "lr": 0}, {"params": groups["fine"], "lr": 0},
-              {"params": groups["color"], "lr": 0}]
+        cam_tensors = self._ba_cameras(optimize_frame, oldest_frame, keyframe_dict, cur[2])
+        pg = [{"params": groups[name], "lr": 0} for name in _STAGE_GROUPS]
         if self.BA:
             pg.append({"params": cam_tensors, "lr": 0})
         optimizer = torch.optim.Adam(pg)
@@ -715,16 +778,9 @@ class Mapper(object):
                         val = val.detach()
                         val[mask] = vg
                         c[key] = val
-            if self.coarse_mapper:
-                self.stage = "coarse"
-            elif joint_iter <= int(num_joint_iters * self.middle_iter_ratio):
-                self.stage = "middle"
-            elif joint_iter <= int(num_joint_iters * self.fine_iter_ratio):
-                self.stage = "fine"
-            else:
-                self.stage = "color"
+            self.stage = self._stage_of(joint_iter, num_joint_iters)
             st = cfg["mapping"]["stage"][self.stage]
-            for gi, name in enumerate(("decoders", "coarse", "middle", "fine", "color")):
+            for gi, name in enumerate(_STAGE_GROUPS):
                 optimizer.param_groups[gi]["lr"] = st[name + "_lr"] * lr_factor
             if self.BA and self.stage == "color":
                 optimizer.param_groups[5]["lr"] = self.BA_cam_lr
@@ -732,30 +788,9 @@ class Mapper(object):
                 self._iter_hook(joint_iter)
 
             optimizer.zero_grad()
-            ro_l, rd_l, gd_l, gc_l = [], [], [], []
-            cam_id = 0
-            for frame in optimize_frame:
-                if frame != -1:
-                    gt_depth, gt_color = self._frame_images(keyframe_dict[frame])
-                    if self.BA and frame != oldest_frame:
-                        c2w = get_camera_from_tensor(cam_tensors[cam_id])
-                        cam_id += 1
-                    else:
-                        c2w = keyframe_dict[frame]["est_c2w"].to(device)
-                else:
-                    gt_depth, gt_color = cur_gt_depth, cur_gt_color
-                    c2w = get_camera_from_tensor(cam_tensors[cam_id]) if self.BA else cur_c2w.to(device)
-                ro, rd, gd, gc = get_samples(0, H, 0, W, pixs_per_image, H, W, fx, fy, cx, cy, c2w, gt_depth,
-                                             gt_color, device, generator=self.generator)
-                ro_l.append(ro.float())
-                rd_l.append(rd.float())
-                gd_l.append(gd.float())
-                gc_l.append(gc.float())
-            rays_o, rays_d = torch.cat(ro_l), torch.cat(rd_l)
-            gt_d, gt_c = torch.cat(gd_l), torch.cat(gc_l)
-            with torch.no_grad():  # Mapper.py:469-481
-                t = (bound.unsqueeze(0) - rays_o.detach().unsqueeze(-1)) / rays_d.detach().unsqueeze(-1)
-                keep = torch.min(torch.max(t, dim=2)[0], dim=1)[0] >= gt_d
+            rays_o, rays_d, gt_d, gt_c = self._window_rays(optimize_frame, oldest_frame, keyframe_dict, cam_tensors,
+                                                           cur, pixs_per_image)
+            keep = inside_mask(rays_o, rays_d, gt_d, bound)  # Mapper.py:469-481
             rays_o, rays_d, gt_d, gt_c = rays_o[keep], rays_d[keep], gt_d[keep], gt_c[keep]
             depth, uncertainty, color = self.renderer.render_batch_ray(
                 c, self.decoders, rays_d, rays_o, device, self.stage, gt_depth=None if self.coarse_mapper else gt_d)
@@ -778,19 +813,7 @@ class Mapper(object):
 
         for p, rg in saved_rg.items():
             p.requires_grad_(rg)
-        if not self.BA:
-            return None
-        cam_id = 0
-        for frame in optimize_frame:
-            if frame != -1:
-                if frame != oldest_frame:
-                    c2w = get_camera_from_tensor(cam_tensors[cam_id].detach())
-                    keyframe_dict[frame]["est_c2w"] = torch.cat([c2w, bottom], 0).clone()
-                    cam_id += 1
-            else:
-                c2w = get_camera_from_tensor(cam_tensors[-1].detach())
-                cur_c2w = torch.cat([c2w, bottom], 0).clone()
-        return cur_c2w
+        return self._ba_write_back(optimize_frame, oldest_frame, keyframe_dict, cam_tensors, cur[2])
 
     def _optimize_map_imap(self, num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
                            keyframe_dict, keyframe_list, cur_c2w):
@@ -798,56 +821,25 @@ class Mapper(object):
         grids and no inside mask; every iteration is stage 'color' with the colour loss and the 0.0005 |sigma|
         regulation term (Mapper.py:490-503); one Adam group over all decoder parameters at imap_decoders_lr
         under StepLR(200, 0.8), plus the BA cameras at BA_cam_lr (Mapper.py:342-345, 380-389, 420-424)."""
-        H, W, fx, fy, cx, cy = self.H, self.W, self.fx, self.fy, self.cx, self.cy
-        cfg, device = self.cfg, self.device
-        bottom = torch.tensor([[0, 0, 0, 1.0]], dtype=torch.float32, device=device)
-        cur_gt_depth = cur_gt_depth.to(device)
-        cur_gt_color = cur_gt_color.to(device).float()
-        cur_c2w = cur_c2w.to(device)
-        optimize_frame, oldest_frame = self._select_window(keyframe_dict, keyframe_list, cur_gt_color, cur_gt_depth,
-                                                           cur_c2w)
-        self._record_selected(idx, optimize_frame, keyframe_dict, keyframe_list, gt_cur_c2w, cur_c2w)
+        device = self.device
+        cur, optimize_frame, oldest_frame = self._autograd_window(idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
+                                                                  keyframe_dict, keyframe_list, cur_c2w)
         pixs_per_image = self.mapping_pixels // len(optimize_frame)
-        params = list(self.decoders.parameters())
-        cam_tensors = []
-        if self.BA:
-            for frame in optimize_frame:
-                if frame != oldest_frame:
-                    c2w = keyframe_dict[frame]["est_c2w"] if frame != -1 else cur_c2w
-                    cam_tensors.append(get_tensor_from_camera(c2w).to(device).requires_grad_(True))
-        pg = [{"params": params, "lr": 0}]
+        cam_tensors = self._ba_cameras(optimize_frame, oldest_frame, keyframe_dict, cur[2])
+        pg = [{"params": list(self.decoders.parameters()), "lr": 0}]
         if self.BA:
             pg.append({"params": cam_tensors, "lr": 0})
         optimizer = torch.optim.Adam(pg)
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=200, gamma=0.8)
         for joint_iter in range(num_joint_iters):
             self.stage = "color"
-            optimizer.param_groups[0]["lr"] = cfg["mapping"]["imap_decoders_lr"]
+            optimizer.param_groups[0]["lr"] = self.cfg["mapping"]["imap_decoders_lr"]
             if self.BA:
                 optimizer.param_groups[1]["lr"] = self.BA_cam_lr
             if self._iter_hook is not None:
                 self._iter_hook(joint_iter)
-            ro_l, rd_l, gd_l, gc_l = [], [], [], []
-            cam_id = 0
-            for frame in optimize_frame:
-                if frame != -1:
-                    gt_depth, gt_color = self._frame_images(keyframe_dict[frame])
-                    if self.BA and frame != oldest_frame:
-                        c2w = get_camera_from_tensor(cam_tensors[cam_id])
-                        cam_id += 1
-                    else:
-                        c2w = keyframe_dict[frame]["est_c2w"].to(device)
-                else:
-                    gt_depth, gt_color = cur_gt_depth, cur_gt_color
-                    c2w = get_camera_from_tensor(cam_tensors[cam_id]) if self.BA else cur_c2w.to(device)
-                ro, rd, gd, gc = get_samples(0, H, 0, W, pixs_per_image, H, W, fx, fy, cx, cy, c2w, gt_depth,
-                                             gt_color, device, generator=self.generator)
-                ro_l.append(ro.float())
-                rd_l.append(rd.float())
-                gd_l.append(gd.float())
-                gc_l.append(gc.float())
-            rays_o, rays_d = torch.cat(ro_l), torch.cat(rd_l)
-            gt_d, gt_c = torch.cat(gd_l), torch.cat(gc_l)
+            rays_o, rays_d, gt_d, gt_c = self._window_rays(optimize_frame, oldest_frame, keyframe_dict, cam_tensors,
+                                                           cur, pixs_per_image)
             depth, uncertainty, color = self.renderer.render_batch_ray(self.c, self.decoders, rays_d, rays_o, device,
                                                                        self.stage, gt_depth=gt_d)
             dm = gt_d > 0
@@ -862,19 +854,7 @@ class Mapper(object):
             optimizer.step()
             scheduler.step()
             optimizer.zero_grad()
-        if not self.BA:
-            return None
-        cam_id = 0
-        for frame in optimize_frame:
-            if frame != -1:
-                if frame != oldest_frame:
-                    c2w = get_camera_from_tensor(cam_tensors[cam_id].detach())
-                    keyframe_dict[frame]["est_c2w"] = torch.cat([c2w, bottom], 0).clone()
-                    cam_id += 1
-            else:
-                c2w = get_camera_from_tensor(cam_tensors[-1].detach())
-                cur_c2w = torch.cat([c2w, bottom], 0).clone()
-        return cur_c2w
+        return self._ba_write_back(optimize_frame, oldest_frame, keyframe_dict, cam_tensors, cur[2])
 
     # -- the frame loop (Mapper.run, Mapper.py:542-657) --------------------------------------------
     _iter_hook = None  # map_frame(): called as hook(joint_iter) before each mapping iteration (the visualiser)

@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from . import common as _common
-from .common import camera_tensors, get_camera_from_tensor, get_samples, get_tensor_from_camera
+from .common import (camera_tensors, constant_speed_guess, get_camera_from_tensor, get_samples,
+                     get_tensor_from_camera, inside_mask, pose4)
 
 _SELECT_UV = _common.select_uv
 
@@ -72,10 +73,7 @@ class Tracker(object):
         """Tracker.py:95-100: keep rays whose AABB exit distance >= gt depth."""
         if self._bound_dev is None or self._bound_dev.device != rays_o.device:
             self._bound_dev = self.bound.to(rays_o.device)
-        with torch.no_grad():
-            t = (self._bound_dev.unsqueeze(0) - rays_o.detach().unsqueeze(-1)) / rays_d.detach().unsqueeze(-1)
-            t, _ = torch.min(torch.max(t, dim=2)[0], dim=1)
-            return t >= gt_depth
+        return inside_mask(rays_o, rays_d, gt_depth, self._bound_dev)
 
     def optimize_cam_in_batch(self, camera_tensor, gt_color, gt_depth, batch_size, optimizer):
         """One camera iteration: sample pixels, render, uncertainty-weighted L1, backward, step."""
@@ -160,9 +158,7 @@ class Tracker(object):
             return self._track_graph(gt_color, gt_depth, pre_c2w,
                                      prev2_c2w if self.const_speed_assumption else None)
         if self.const_speed_assumption and prev2_c2w is not None:
-            pre = pre_c2w.float().to(device)
-            delta = pre @ torch.linalg.inv_ex(prev2_c2w.to(device).float())[0]  # (no error check: no sync)
-            est = delta @ pre
+            est = constant_speed_guess(pre_c2w.float().to(device), prev2_c2w.to(device).float())
         else:
             est = pre_c2w.to(device)
         # (on the device: no host round trip per frame)
@@ -187,8 +183,7 @@ class Tracker(object):
             loss =self.optimize_cam_in_batch(camera_tensor, gt_color, gt_depth, self.tracking_pixels, optimizer)
             if loss < best_loss:
                 best_loss, best = loss, camera_tensor.clone().detach()
-        bottom = torch.tensor([[0, 0, 0, 1.0]], dtype=torch.float32, device=device)
-        return torch.cat([get_camera_from_tensor(best), bottom], 0)
+        return pose4(get_camera_from_tensor(best))
 
     # -- the frame loop (Tracker.run, Tracker.py:144-258) ------------------------------------------
     def attach_run(self, slam):
@@ -281,8 +276,7 @@ class Tracker(object):
                 self._iter_hook(cam_iter, cam.detach())
             pix = torch.randint(eng.n_window(), (self.tracking_pixels,), device=device, generator=self.generator)
             eng.iteration(cam, depth, color, pix, opt, best=(best_loss, best), **self._lr2())  # (+ Tracker.py:245-247)
-        bottom = torch.tensor([[0, 0, 0, 1.0]], dtype=torch.float32, device=device)
-        return torch.cat([get_camera_from_tensor(best), bottom], 0)
+        return pose4(get_camera_from_tensor(best))
 
     def _track_graph(self, gt_color, gt_depth, pre_c2w, prev2_c2w):
         """track_frame's whole per-frame work as ONE captured hipGraph, replayed for every frame: the pose
@@ -317,7 +311,7 @@ class Tracker(object):
 
         def frame(zero_lr=False):
             pre = st["pre"]
-            est = (pre @ torch.linalg.inv_ex(st["prev2"])[0]) @ pre if speed else pre
+            est = constant_speed_guess(pre, st["prev2"]) if speed else pre
             # the guess's 7-vector into the camera and the best pose in one launch (ABI v22)
             ops.cam_vector_batch(est[None], cam.detach().view(1, 7), best.view(1, 7))
             best_loss.fill_(float("inf"))

@@ -295,6 +295,53 @@ def test_frustum_rows_kernel_matches_mask(loop):
             assert torch.equal(slot, inv), (key, name)
 
 
+def _tiny_frustum_case(tiny):
+    """frustum_rows_device's arguments on the tiny scene's fine grid, with fresh output buffers."""
+    cam = scenes.TINY_CAM
+    b, _, cur = scenes.tiny_window()
+    depth = torch.from_numpy(scenes.box_depth(cur, cam, b, seed=150)).to(DEV)
+    shp = tuple(int(v) for v in tiny["grid_fine"].shape[2:])
+    n = shp[0] * shp[1] * shp[2]
+    args = (shp, depth, torch.from_numpy(b), cam["H"], cam["W"], cam["fx"], cam["fy"], cam["cx"], cam["cy"])
+
+    def buffers():
+        slot, rows = (torch.full((n,), -7, dtype=torch.int32, device=DEV) for _ in range(2))
+        return slot, rows, torch.zeros(1, dtype=torch.int64, device=DEV)
+
+    return torch.from_numpy(cur).to(DEV), args, n, buffers
+
+
+def test_frustum_rows_device_accepts_a_3x4_pose(tiny):
+    c2w, args, n, buffers = _tiny_frustum_case(tiny)
+    assert c2w.shape == (4, 4)
+    out = []
+    for pose in (c2w, c2w[:3]):
+        slot, rows, n_live = buffers()
+        P.mapper.frustum_rows_device(pose, *args, slot, rows, n_live)
+        out.append((slot, rows, n_live))
+    (s4, r4, n4), (s3, r3, n3) = out
+    k = int(n4)
+    assert 0 < k < n
+    assert torch.equal(n3, n4) and torch.equal(s3, s4) and torch.equal(r3[:k], r4[:k])
+
+
+@pytest.mark.parametrize("bad", ["short slot", "float rows", "int32 n_live"])
+def test_frustum_rows_device_refuses_bad_buffers(tiny, bad):
+    """A buffer the kernels would overrun or misread is refused on the host: nothing is launched, nothing written."""
+    c2w, args, n, buffers = _tiny_frustum_case(tiny)
+    slot, rows, n_live = buffers()
+    if bad == "short slot":
+        slot = slot[:n - 1]
+    elif bad == "float rows":
+        rows = rows.float()
+    else:
+        n_live = n_live.int()
+    with pytest.raises(ValueError):
+        P.mapper.frustum_rows_device(c2w, *args, slot, rows, n_live)
+    torch.cuda.synchronize()
+    assert bool((slot == -7).all()) and bool((rows == -7).all()) and int(n_live) == 0
+
+
 @pytest.mark.parametrize("n", [0, 1, 200, 1000, 5000])
 def test_loss_sum_best_matches_torch_and_keeps_the_best_pose(n):
     """ABI v21 nslam_loss_sum_best (the tracker's per-iteration loss and Tracker.py:245-247's best-pose

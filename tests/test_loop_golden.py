@@ -112,6 +112,59 @@ def test_keyframe_overlap_host_matches_reference(loop, P, monkeypatch):
     assert [int(s) for s in sel] == [int(s) for s in loop["overlap.selected"]]
 
 
+def test_frustum_mask_accepts_a_3x4_pose(loop, P):
+    """The projection helper pads a [3,4] pose: the mask is the [4,4] pose's bit for bit."""
+    b, _, cur = scenes.room0_window()
+    cam = scenes.ROOM0_CAM
+    depth = torch.from_numpy(scenes.box_depth(cur, cam, b, seed=int(loop["frustum.depth_seed"])))
+    shp = tuple(int(v) for v in loop["frustum.shape.grid_fine"])
+    c2w = torch.from_numpy(cur)
+    assert c2w.shape == (4, 4)
+    m4, m3 = (P.mapper.frustum_mask(p, "grid_fine", shp, depth, torch.from_numpy(b), cam["H"], cam["W"], cam["fx"],
+                                    cam["fy"], cam["cx"], cam["cy"]) for p in (c2w, c2w[:3]))
+    assert m4.any() and not m4.all()
+    assert torch.equal(m3, m4)
+
+
+@pytest.mark.parametrize("coarse", [False, True])
+@pytest.mark.parametrize("ratios", [(0.4, 0.6), (0.0, 0.0)])  # (the second: the colour-refinement pass)
+@pytest.mark.parametrize("n", [1, 5, 60, 300])
+def test_stage_runs_expand_to_the_stage_rule(P, n, ratios, coarse):
+    mp = overlap_mapper(P, "cpu")
+    mp.coarse_mapper = coarse
+    mp.middle_iter_ratio, mp.fine_iter_ratio = ratios
+    runs = mp._stage_runs(n)
+    assert [s for s, k in runs for _ in range(k)] == [mp._stage_of(i, n) for i in range(n)]
+    assert all(k > 0 for _, k in runs) and all(a[0] != b[0] for a, b in zip(runs, runs[1:]))
+    if coarse:
+        assert runs == [("coarse", n)]
+
+
+@pytest.mark.parametrize("selected,keyframe_list,window,oldest", [
+    ([], [], [-1], None),                              # no keyframes
+    ([], [0], [0, -1], 0),                             # one keyframe: it is the last and the oldest
+    ([0, 2], [0, 5, 10, 15], [0, 2, 3, -1], 0),        # the selection already contains the oldest
+    ([2, 1], [0, 5, 10, 15], [2, 1, 3, -1], 1),
+    ([], [0, 5, 10], [2, -1], 2),                      # nothing overlaps: the last keyframe alone
+])
+def test_window_tail(P, selected, keyframe_list, window, oldest):
+    """Mapper._window_of == the statements of Mapper.py:268-272, 346-349 (restated here) for a given selection;
+    numpy integers as keyframe_selection_overlap returns them; the selection is not modified."""
+    def reference_tail(optimize_frame):
+        oldest_frame = None
+        if len(keyframe_list) > 0:
+            optimize_frame = optimize_frame + [len(keyframe_list) - 1]
+            oldest_frame = min(optimize_frame)
+        optimize_frame += [-1]
+        return optimize_frame, oldest_frame
+
+    for sel in (list(selected), list(np.asarray(selected, dtype=np.int64))):
+        before = list(sel)
+        got = P.Mapper._window_of(sel, keyframe_list)
+        assert sel == before
+        assert got == reference_tail(list(sel)) == (window, oldest)
+
+
 def test_scene_helpers_deterministic():
     """The shared frame generator is pure numpy: the same seed gives the same bits."""
     b, poses, cur = scenes.room0_window()
