@@ -202,7 +202,8 @@ def test_fused_adam_live_count_matches_exact_rows(n_vox):
     """ABI v19 n_live: a row-masked segment sized for a capacity (row list and Adam state for every voxel,
     compact gradient [capacity][32]) whose live count is a device word updates exactly what a segment of
     the live rows alone does — bit for bit — and nothing else; with a capacity far above the live count
-    (30000 voxels: the launch is capped at 512 workgroups that stride the live rows) too."""
+    (30000 voxels: 235 workgroups of 128 rows, below the cap of 512, so every workgroup makes at most one
+    pass; the stride loop beyond 65536 live rows: test_gpu_update_edges.py) too."""
     g = torch.Generator(device=DEV).manual_seed(1)
     Z = n_vox // 42
     grid = torch.randn(1, 32, Z, 6, 7, device=DEV, generator=g).contiguous(memory_format=torch.channels_last_3d)
