@@ -20,8 +20,10 @@ the frustum-selected voxels in place instead of through masked copies (Mapper.py
 """
 from __future__ import annotations
 
+import collections
 import ctypes
-import math
+import dataclasses
+import functools
 import os
 import weakref
 
@@ -30,7 +32,6 @@ import torch
 
 from . import _lib, ops
 from ._lib import check, lib, ptr, stream_ptr
-from .common import get_camera_from_tensor
 
 _GRID_OF = {"coarse": "grid_coarse", "middle": "grid_middle", "fine": "grid_fine", "color": "grid_color"}
 
@@ -42,6 +43,148 @@ def _env_choice(name, default, allowed):
     if v not in allowed:
         raise ValueError(f"{name}={v!r}: expected one of {sorted(allowed)}")
     return v
+
+
+def env_knobs():
+    """The MappingEngine attributes that take their default from the environment."""
+    return {
+        # concurrent backward: enqueue the colour weight-gradient branch before the grid-gradient one
+        # (its workgroups are dispatched first and hold one slot per CU; the lean launch fills the rest)
+        "wgrad_first": _env_choice("NSLAM_WGRAD_FIRST", "1", ("0", "1")) == "1",
+        # the ray prefetch's stream: the backward's first side stream ("lean", default: one side queue
+        # fewer in a captured iteration) or its own ("own"); and one Adam call for the whole update on that
+        # stream once both backward branches are done (NSLAM_ADAM_MERGE=1, default) instead of one per
+        # branch (0).  A/B: profiles/r05_experiments/ab_defaults.txt
+        "prefetch_stream": _env_choice("NSLAM_PREFETCH_STREAM", "lean", ("lean", "own")),
+        "adam_merge": _env_choice("NSLAM_ADAM_MERGE", "1", ("0", "1")) == "1",
+        # live-point lists (nslam_live_points): the mask-only backward of a mapping iteration without d/dpts
+        # runs only the points that touch a frustum-selected voxel of the decoder's grid — with compacted
+        # grid gradients the others add nothing.  The lists ride with the ray batch.  0: every point, as
+        # nslam_query_bwd_decoders.  Measured on the synthetic room0 window only (about half of the kept
+        # points are dead there); the dead share of a real sequence has not been measured.
+        "live_points": _env_choice("NSLAM_LIVE_POINTS", "1", ("0", "1")) == "1",
+    }
+
+
+BackwardPlan = collections.namedtuple("BackwardPlan", "units streams has_wgrad merge_adam")
+
+
+def backward_plan(decs, dec_grads, *, masks, tape, n, merge=True, wgrad_first=True, adam_merge=True,
+                  concurrent=True, has_on_branch=True, ordered=False):
+    """Which launches the backward of a stage's decoders `decs` consists of, and where each runs — no tensor,
+    no stream.  dec_grads: the decoders with parameter gradients; masks / tape: the forward left ReLU masks / the
+    colour decoder's activation tape; n: points; merge, wgrad_first, adam_merge, concurrent: the engine's
+    knobs; has_on_branch: the caller updates per branch; ordered: its branch work must keep one order
+    (query_bwd ordered_branches).  Returns
+      units       ((kind, decoder names), ...) in enqueue order, kind =
+                    "wgrad"  the colour decoder's parameter gradients from the tape (nslam_color_wgrad),
+                    "lean"   the named decoders' grid gradients (and d/dpts) from the masks, one launch,
+                    "one"    a decoder's whole backward by itself (nslam_query_bwd_decoder);
+      streams     per unit: 0 = the caller's stream, k = the k-th side stream;
+      has_wgrad   a "wgrad" unit exists (the colour grid and decoder are then updated after it AND "lean");
+      merge_adam  the whole update is one call on the lean launch's stream once both units are done."""
+    wgt = [d for d in decs if d in dec_grads]
+    tape_color = "color" in wgt and masks and tape
+    lean = tuple(d for d in decs if merge and masks and (d not in wgt or (d == "color" and tape_color)))
+    units = []
+    if "color" in lean and "color" in wgt and n > 0:
+        units.append(("wgrad", ("color",)))
+    if lean:
+        units.append(("lean", lean))
+    units += [("one", (d,)) for d in decs if d not in lean]
+    if not wgrad_first:
+        units.sort(key=lambda u: u[0] == "wgrad")
+    has_wgrad = any(kind == "wgrad" for kind, _ in units)
+    merge_adam = bool(adam_merge and has_wgrad and has_on_branch and not ordered and wgrad_first and concurrent
+                      and len(units) == 2 and units[1][0] == "lean")
+    par = concurrent and len(units) > 1
+    return BackwardPlan(tuple(units), tuple(i if par else 0 for i in range(len(units))), has_wgrad, merge_adam)
+
+
+def _dec_table(names, ptr_of):
+    """(4-slot pointer table indexed by NSLAM_DEC_*, bit mask of `names`): slot of a name = ptr_of(name)."""
+    tab, mask = (ctypes.c_void_p * 4)(), 0
+    for name in names:
+        d = ops._DEC_ID[name]
+        mask |= 1 << d
+        tab[d] = ptr_of(name)
+    return tab, mask
+
+
+def _live_tables(decs, names, idx, nl):
+    """The tables of `names` into live_lists' (idx [decoders of the stage `decs`, N*S], nl [4]), and their mask."""
+    ips, mask = _dec_table(names, lambda name: idx[decs.index(name)].data_ptr())
+    return ips, _dec_table(names, lambda name: nl[ops._DEC_ID[name]:].data_ptr())[0], mask
+
+
+@dataclasses.dataclass
+class RayBatch:
+    """The rays of one iteration: gather_rays' outputs, the sampler's z and, with live-point lists, live_lists'
+    (per decoder of the stage the indices of its live points, and their counts by NSLAM_DEC_*)."""
+    ro: torch.Tensor
+    rd: torch.Tensor
+    gd: torch.Tensor
+    gc: torch.Tensor
+    keep: torch.Tensor
+    z: torch.Tensor
+    live_idx: torch.Tensor = None
+    n_live: torch.Tensor = None
+
+    @property
+    def live(self):
+        return None if self.live_idx is None else (self.live_idx, self.n_live)
+
+    def empty_like(self):
+        return RayBatch(*(t if t is None else torch.empty_like(t) for t in vars(self).values()))
+
+
+class PrefetchRing:
+    """The two persistent ray batches that prefetching iterations alternate between (MappingEngine._parity:
+    which one holds this iteration's): a hipGraph of an even and one of an odd iteration replay in turn with
+    no copies.  A prefetched batch is valid only for its key and the very frames (images and poses, unmodified)
+    it was gathered from: held by weak reference (identity — a new tensor at a freed one's address is not the
+    same frame) and version counter; a call with other frames or poses changed in place draws its own batch.
+    The version check cannot see a kernel's writes: a caller whose camera step can move the poses passes
+    prefetch=False (Mapper: bundle adjustment's colour stage, where the cameras' lr is not 0).
+    live_gen[k]: the (layout_gen, rows_gen) set k's live-point lists were formed at; a set whose lists are older
+    than the slot maps (set_rows, bind_masks, Mapper._bind_frustum) keeps its rays and gets new lists before
+    use.  A captured hipGraph of prefetching iterations replays the lists of its capture-time ordering: rebind
+    rows only before a replay whose first iteration draws its own batch (Mapper.optimize_map's graphs do)."""
+
+    def __init__(self):
+        self.stream = None  # (survives drop(): a captured graph and the next one share it)
+        self.drop()
+
+    def drop(self):
+        self.key, self.frames, self.sets, self.live_gen = None, [], [None, None], [None, None]
+
+    def valid_for(self, key, ftens):
+        return (self.key is not None and self.key == key and len(self.frames) == len(ftens)
+                and all(r() is t and v == t._version for (r, v), t in zip(self.frames, ftens)))
+
+    def start(self, key, ftens, first, gen):
+        """A new run: `first` is its first iteration's batch (set 0); set 1 has the same shapes."""
+        self.key, self.frames = key, [(weakref.ref(t), t._version) for t in ftens]
+        self.sets, self.live_gen = [first, first.empty_like()], [gen, None]
+
+    def current(self, parity):
+        return self.sets[parity]
+
+    def next(self, parity):
+        return self.sets[1 - parity]
+
+    def side_stream(self, eng):
+        """The stream the next batch is drawn on, chosen on first use."""
+        if self.stream is None:
+            if eng.prefetch_stream == "lean" and eng.wgrad_first and eng.concurrent:
+                # the mask-only launch's stream: the prefetch is done long before that stream's backward work.
+                # In any other topology that side stream carries the weight-gradient branch
+                if not eng._side:
+                    eng._side.append(torch.cuda.Stream(eng.device))
+                self.stream = eng._side[0]
+            else:
+                self.stream = torch.cuda.Stream(eng.device)
+        return self.stream
 
 
 class FlatDecoder:
@@ -104,42 +247,17 @@ class MappingEngine:
         self._tape = None   # colour-decoder activation tape of the last query_fwd (ABI v9)
         self.occ_add = None  # middle occupancy of the last deferred-combine query_fwd
         self._draws = None   # (seed, ops.PixelDraws) of in-kernel pixel draws
-        self._pre = None     # (key, [buffer set 0, buffer set 1]) ray batches of the prefetch loop
-        self._parity = 0     # which set holds this iteration's batch
-        self._pre_stream = None
-        self._live_gen = [None, None]  # (layout_gen, rows_gen) each buffer set's live-point lists were formed at
+        self.ring = PrefetchRing()  # the ray batches of a prefetching run of iterations
+        self._parity = 0     # which of its two sets holds this iteration's batch
         self._side = []     # side streams of the concurrent decoder backward
         self.concurrent = True
-        # concurrent backward: enqueue the colour weight-gradient branch before the grid-gradient one
-        # (its workgroups are dispatched first and hold one slot per CU; the lean launch fills the rest)
-        self.wgrad_first = _env_choice("NSLAM_WGRAD_FIRST", "1", ("0", "1")) == "1"
         # every mask-only decoder backward as ONE launch (ABI v10); False: one nslam_query_bwd_decoder
         # launch per decoder (the library then runs a colour tape backward's two kernels in sequence)
         self.merge = True
-        self._lean_ev = None
-        # where the ray prefetch of the next iteration forks off the main stream: "start" (beside the
-        # forward) or "after_fwd" (beside the loss and the backward: the forward's waves then have every
-        # wave slot of the chip; a prefetch sampler wave resident on a SIMD leaves room for only two of
-        # the forward's three)
-        self.prefetch_at = _env_choice("NSLAM_PREFETCH_AT", "start", ("start", "after_fwd"))
-        # the ray prefetch's stream: the backward's first side stream ("lean", default: one side queue
-        # fewer in a captured iteration) or its own ("own"); and one Adam call for the whole update on that
-        # stream once both backward branches are done (NSLAM_ADAM_MERGE=1, default) instead of one per
-        # branch (0).  A/B, round 5: 0.2177 / 0.2150 / 0.2129 ms per room0 iteration (own, lean, lean +
-        # merged Adam; medians of 3 alternating rounds, profiles/r05_experiments/ab_defaults.txt)
-        self.prefetch_stream = _env_choice("NSLAM_PREFETCH_STREAM", "lean", ("lean", "own"))
-        self.adam_merge = _env_choice("NSLAM_ADAM_MERGE", "1", ("0", "1")) == "1"
-        # where the merged Adam runs: after the mask-only launch on its side stream ("side") or on the
-        # main stream after the join ("main", experiment)
-        self.adam_on = _env_choice("NSLAM_ADAM_ON", "side", ("side", "main"))
-        self._wg_ev = None
-        # live-point lists (nslam_live_points): the mask-only backward of a mapping iteration without d/dpts
-        # runs only the points that touch a frustum-selected voxel of the decoder's grid — with compacted
-        # grid gradients the others add nothing.  The lists belong to the ray batch: iteration() forms them
-        # right after the sampler (with prefetch: an iteration ahead, on the side stream).  0: every point,
-        # as nslam_query_bwd_decoders.  Measured on the synthetic room0 window only (about half of the kept
-        # points are dead there); the dead share of a real sequence has not been measured.
-        self.live_points = _env_choice("NSLAM_LIVE_POINTS", "1", ("0", "1")) == "1"
+        self._lean_ev = self._wg_ev = None  # persistent events (never destroyed mid-capture), made on first use
+        knobs = env_knobs()
+        self.wgrad_first, self.adam_merge = knobs["wgrad_first"], knobs["adam_merge"]
+        self.prefetch_stream, self.live_points = knobs["prefetch_stream"], knobs["live_points"]
         self.rows_gen = 0  # bumped whenever a slot map is rewritten in place (bind_masks, Mapper._bind_frustum)
         for k, v in c.items():
             if not v.is_contiguous(memory_format=torch.channels_last_3d):
@@ -257,7 +375,9 @@ class MappingEngine:
         return full[:ar.numel()], n_live
 
     # -- query in ray form ---------------------------------------------------------------------
-    def _cfg(self, stage, ro, rd, z, grid_grads, dec_grads):
+    def _cfg(self, stage, ro, rd, z, grid_grads, dec_grads, masks=None, tape=None):
+        """The query descriptor of a ray batch; masks / tape: the forward's ReLU masks and activation tape
+        (written by query_fwd, read by query_bwd; live_lists needs neither)."""
         decs = ops._DEC_FOR_STAGE[stage]
         meta = ops.QueryMeta(stage, decs, {n: self.decs[n].packer for n in decs},
                              {n: self.dec_bounds[n] for n in decs}, self.oob, None)
@@ -270,8 +390,8 @@ class MappingEngine:
         dg = {n: self.decs[n].grad for n in decs if n in dec_grads}
         cfg = ops._fill_cfg(meta, pairs, packed, dg, False)
         cfg.rays_o, cfg.rays_d, cfg.z_vals, cfg.n_samples = ptr(ro), ptr(rd), ptr(z), z.shape[1]
-        cfg.saved_masks = ptr(self._saved)
-        cfg.act_tape = ptr(self._tape)
+        cfg.saved_masks = ptr(masks)
+        cfg.act_tape = ptr(tape)
         return cfg
 
     def live_lists(self, stage, ro, rd, z, out=None):
@@ -286,19 +406,8 @@ class MappingEngine:
                    torch.zeros(4, dtype=torch.int64, device=z.device))
         idx, nl = out
         keys = tuple(_GRID_OF[d] for d in decs) if self.grid_grads else ()
-        saved, tape = self._saved, self._tape
-        self._saved = self._tape = None  # (the lists need neither)
-        try:
-            cfg = self._cfg(stage, ro, rd, z, keys, ())
-        finally:
-            self._saved, self._tape = saved, tape
-        ips, nps = (ctypes.c_void_p * 4)(), (ctypes.c_void_p * 4)()
-        mask = 0
-        for i, name in enumerate(decs):
-            d = ops._DEC_ID[name]
-            mask |= 1 << d
-            ips[d] = idx[i].data_ptr()
-            nps[d] = nl[d:d + 1].data_ptr()
+        cfg = self._cfg(stage, ro, rd, z, keys, ())
+        ips, nps, mask = _live_tables(decs, decs, idx, nl)
         wsb = lib().nslam_live_points_workspace_size(n)
         ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=z.device)
         with ops._span("live_points"):
@@ -317,187 +426,141 @@ class MappingEngine:
         self._tape = None
         if tape and stage == "color":
             self._tape = torch.empty(lib().nslam_query_tape_size(n) // 4, dtype=torch.float32, device=z.device)
-        cfg = self._cfg(stage, ro, rd, z, (), ())
+        cfg = self._cfg(stage, ro, rd, z, (), (), masks=self._saved, tape=self._tape)
         self.occ_add = ops.query_fwd_launch(cfg, None, n, raw, defer_occ=defer_occ)
         return raw
 
     def query_bwd(self, stage, ro, rd, z, g_raw, grid_grads, dec_grads, concurrent=None, pts_grad=False,
                   on_branch=None, pts_parts=False, ordered_branches=False, on_pts=None, live=None):
-        """Backward into the engine's gradient buffers, as independent launches ("branches") that write
-        disjoint buffers:
-          lean     every decoder's grid gradient (and d/dpts) from the forward's ReLU masks, ONE launch
-                   (ABI v10 nslam_query_bwd_decoders; the trainable colour decoder included);
-          wgrad    the colour decoder's parameter gradients (ABI v16 nslam_color_wgrad), which reads only
-                   the forward's tapes and g_raw — so it runs beside the lean launch;
-          others   a decoder with parameter gradients and no tape path (nslam_query_bwd_decoder each).
-        With `concurrent` the branches run on separate streams (parallel branches of a captured hipGraph).
-
-        pts_grad: also return d loss / d pts [N*S, 3] float64 (tracking, bundle adjustment): every
-        decoder writes its share into its own buffer and the shares are summed afterwards (or returned
-        as a list with pts_parts).
-        on_branch(names, part): called on a branch's stream once what it updates is complete — "grids":
-        the grids of the lean launch's decoders but the colour one; "all": the colour grid and the
-        colour decoder, on the weight-gradient branch after it AND the lean launch (k_color_wgrad reads
-        the colour grid: it is not rewritten before that kernel is done); "unit": a per-decoder launch's
-        grid and parameters — the per-branch Adam of the mapping iteration.
-        ordered_branches: the weight-gradient branch's on_branch starts only after the lean branch's
-        on_branch work (not just the lean launch) — for collectives issued there on two communicators,
-        which every rank must then run in the same order (distributed.ShardedAdamExchange).
-        on_pts(parts): with pts_grad, called once every decoder's d/dpts share is written — on the lean
-        launch's stream right after it when that launch forms all of them (bundle adjustment's camera
-        gradient then runs beside the weight gradients, not after the join), else on the caller's stream
-        after the join.
-        live: live_lists() of this very batch and the current slot maps — the lean launch then runs each
-        decoder's live points only (nslam_query_bwd_decoders_live; ignored with pts_grad, which needs
-        every point)."""
+        """Backward into the engine's gradient buffers, as the independent launches ("branches", writing disjoint
+        buffers) that backward_plan lists.  Here they are forked off the caller's stream, enqueued — each followed by
+        the update that may start after it — and joined; with `concurrent` on separate streams (parallel branches of
+        a captured hipGraph).
+        pts_grad: also return d loss / d pts [N*S, 3] float64 (tracking, bundle adjustment): every decoder writes
+        its share into its own buffer and the shares are summed afterwards (or returned as a list with pts_parts).
+        on_branch(names, part): called on a branch's stream once what it updates is complete — "grids": the grids of
+        the lean launch's decoders but the colour one; "all": the colour grid and the colour decoder, on the
+        weight-gradient branch after it AND the lean launch (k_color_wgrad reads the colour grid: it is not
+        rewritten before that kernel is done); "unit": a per-decoder launch's grid and parameters — the per-branch
+        Adam of the mapping iteration.
+        ordered_branches: the weight-gradient branch's on_branch starts only after the lean branch's on_branch work
+        (not just the lean launch) — for collectives issued there on two communicators, which every rank must then
+        run in the same order (distributed.ShardedAdamExchange).
+        on_pts(parts): with pts_grad, called once every decoder's d/dpts share is written — on the lean launch's
+        stream right after it when that launch forms all of them (bundle adjustment's camera gradient then runs
+        beside the weight gradients, not after the join), else on the caller's stream after the join.
+        live: live_lists() of this very batch and the current slot maps — the lean launch then runs each decoder's
+        live points only (nslam_query_bwd_decoders_live; ignored with pts_grad, which needs every point)."""
         n = z.numel()
         self._clean = False
-        concurrent = self.concurrent if concurrent is None else concurrent
-        cfg = self._cfg(stage, ro, rd, z, grid_grads, dec_grads)
+        live = None if pts_grad else live
+        cfg = self._cfg(stage, ro, rd, z, grid_grads, dec_grads, masks=self._saved, tape=self._tape)
         cfg.need_pts_grad = int(bool(pts_grad))
-        if pts_grad:
-            live = None
         decs = list(ops._DEC_FOR_STAGE[stage])
-        wgt = [d for d in decs if d in dec_grads]
-        masks = self._saved is not None
-        tape_color = "color" in wgt and masks and self._tape is not None
-        lean = [d for d in decs if self.merge and masks and (d not in wgt or (d == "color" and tape_color))]
-        others = [d for d in decs if d not in lean]
+        plan = backward_plan(decs, dec_grads, masks=self._saved is not None, tape=self._tape is not None, n=n,
+                             merge=self.merge, wgrad_first=self.wgrad_first, adam_merge=self.adam_merge,
+                             concurrent=self.concurrent if concurrent is None else concurrent,
+                             has_on_branch=on_branch is not None, ordered=ordered_branches)
         gp = {d: torch.empty(n, 3, dtype=torch.float64, device=z.device) for d in decs} if pts_grad else None
-        # units: (kind, decoder names) in enqueue order
-        units = []
-        if "color" in lean and "color" in wgt and n > 0:
-            units.append(("wgrad", ["color"]))
-        if lean:
-            units.append(("lean", lean))
-        units += [("one", [d]) for d in others]
-        if not self.wgrad_first:
-            units.sort(key=lambda u: u[0] == "wgrad")
-        has_wgrad = any(u[0] == "wgrad" for u in units)
-        merged_names = None
-        # NSLAM_ADAM_MERGE=1: one Adam call after both branches, on the lean launch's stream
-        merge_adam = (self.adam_merge and has_wgrad and on_branch is not None and not ordered_branches
-                      and self.wgrad_first and concurrent and len(units) == 2 and units[1][0] == "lean")
-        wgrad_st = None
         main = torch.cuda.current_stream(z.device)
-        par = concurrent and len(units) > 1
-        streams = [main]
-        if par:
-            while len(self._side) < len(units) - 1:
-                self._side.append(torch.cuda.Stream(z.device))
-            streams += self._side[:len(units) - 1]
-        used = streams[1:]
+        while len(self._side) < max(plan.streams):
+            self._side.append(torch.cuda.Stream(z.device))
+        streams = [main] + self._side[:max(plan.streams)]
+        if plan.has_wgrad and self._lean_ev is None:
+            self._lean_ev = torch.cuda.Event()
+        if plan.merge_adam and self._wg_ev is None:
+            self._wg_ev = torch.cuda.Event()
+        wgrad_st = None
         with ops._span("query_bwd"):
-            for st in used:  # fork: every branch starts from the same point of the main stream
+            for st in streams[1:]:  # fork: every branch starts from the same point of the main stream
                 st.wait_stream(main)
                 for t in (ro, rd, z, g_raw, self._saved, self._tape) + (tuple(live) if live else ()):
                     if t is not None:
                         t.record_stream(st)
-            for i, (kind, names) in enumerate(units):
-                st = streams[i] if par else main
+            for (kind, names), si in zip(plan.units, plan.streams):
+                st = streams[si]
                 with torch.cuda.stream(st):
                     if kind == "wgrad":
-                        wsb = lib().nslam_query_bwd_decoder_workspace_size(ctypes.byref(cfg), _lib.DEC_COLOR, n)
-                        ws = torch.empty(wsb, dtype=torch.uint8, device=z.device)
-                        with ops._span("query_bwd.color_wgrad"):
-                            rc = lib().nslam_color_wgrad(ctypes.byref(cfg), None, n, ptr(g_raw), ptr(ws), wsb,
-                                                         st.cuda_stream)
-                        check(rc, "nslam_color_wgrad")
-                        wgrad_st = st  # (its update waits for the lean launch: see below)
-                        if merge_adam:
-                            if self._wg_ev is None:
-                                self._wg_ev = torch.cuda.Event()
+                        self._launch_wgrad(cfg, n, g_raw, st)
+                        wgrad_st = st  # (its update waits for the lean launch: below)
+                        if plan.merge_adam:
                             self._wg_ev.record(st)
                     elif kind == "lean":
-                        lc = _lib.NslamQueryCfg.from_buffer_copy(cfg)  # grids (and d/dpts) only
-                        gps = (ctypes.c_void_p * 4)()
-                        mask = 0
-                        for name in names:
-                            d = ops._DEC_ID[name]
-                            mask |= 1 << d
-                            lc.dgrad[d] = _lib.NslamDecGrad()
-                            if pts_grad:
-                                gps[d] = ptr(gp[name])
-                        with ops._span("query_bwd." + "+".join(names)):
-                            if live is not None:
-                                ips, nps = (ctypes.c_void_p * 4)(), (ctypes.c_void_p * 4)()
-                                for name in names:
-                                    d = ops._DEC_ID[name]
-                                    ips[d] = live[0][decs.index(name)].data_ptr()
-                                    nps[d] = live[1][d:d + 1].data_ptr()
-                                rc = lib().nslam_query_bwd_decoders_live(ctypes.byref(lc), mask, None, n, ptr(g_raw),
-                                                                         ips, nps, st.cuda_stream)
-                            else:
-                                rc = lib().nslam_query_bwd_decoders(ctypes.byref(lc), mask, None, n, ptr(g_raw),
-                                                                    gps, st.cuda_stream)
-                        check(rc, "nslam_query_bwd_decoders")
+                        self._launch_lean(cfg, decs, names, n, g_raw, st, gp, live)
                         if on_pts is not None and pts_grad and set(names) == set(decs):
-                            for name in names:  # (allocated on the caller's stream)
-                                gp[name].record_stream(st)
                             on_pts([gp[d] for d in decs])
                             on_pts = None
-                        if has_wgrad and self._lean_ev is None:  # one persistent event (never destroyed mid-capture)
-                            self._lean_ev = torch.cuda.Event()
-                        if has_wgrad and not ordered_branches:
+                        if plan.has_wgrad and not ordered_branches:
                             self._lean_ev.record(st)
-                        if on_branch is not None and merge_adam and self.adam_on == "main":
-                            merged_names = names  # (the merged Adam runs on the main stream after the join)
-                        elif on_branch is not None and merge_adam:
-                            # every update of the iteration in one Adam call on this stream, once the
+                        if on_branch is not None and plan.merge_adam:
+                            # merged Adam: every update of the iteration in one call on this stream, once the
                             # weight-gradient branch (its slab reduction; its colour-grid gathers) is done
                             st.wait_event(self._wg_ev)
-                            on_branch(names, part="all")
+                            on_branch(list(names), part="all")
                         elif on_branch is not None:
-                            # the grids of this launch — but the colour grid, which k_color_wgrad reads (its
-                            # colour feature) and which is updated on that branch once both are done.  A
-                            # trainable decoder here without a weight-gradient branch (no points) still
-                            # takes its Adam step (torch's Adam steps a parameter whose gradient is zero)
-                            own = [d for d in names if not (d == "color" and has_wgrad)]
-                            dec_here = not has_wgrad and any(d in wgt for d in own)
+                            # per-branch Adam: the grids of this launch — but the colour grid, which
+                            # k_color_wgrad reads and which is updated on that branch once both are done.  A
+                            # trainable decoder here (no points: no weight-gradient branch) still takes its step
+                            own = [d for d in names if not (d == "color" and plan.has_wgrad)]
+                            dec_here = not plan.has_wgrad and any(d in dec_grads for d in own)
                             if own:
                                 on_branch(own, part="all" if dec_here else "grids")
-                        if has_wgrad and ordered_branches:
-                            self._lean_ev.record(st)
+                        if plan.has_wgrad and ordered_branches:
+                            self._lean_ev.record(st)  # ordered variant: after this branch's on_branch work too
                     else:
-                        name = names[0]
-                        d = ops._DEC_ID[name]
-                        wsb = lib().nslam_query_bwd_decoder_workspace_size(ctypes.byref(cfg), d, n)
-                        ws = torch.empty(wsb, dtype=torch.uint8, device=z.device) if wsb else None
-                        with ops._span("query_bwd." + name):
-                            rc = lib().nslam_query_bwd_decoder(ctypes.byref(cfg), d, 0, None, n, ptr(g_raw),
-                                                               ptr(gp[name]) if pts_grad else None, ptr(ws), wsb,
-                                                               st.cuda_stream)
-                        check(rc, "nslam_query_bwd_decoder")
-                        if on_branch is not None:
-                            on_branch(names, part="unit")
+                        self._launch_one(cfg, names[0], n, g_raw, st, gp)
+                        if on_branch is not None:  # per-branch Adam of a per-decoder launch
+                            on_branch(list(names), part="unit")
                 if pts_grad and st is not main:
                     for name in names:
-                        gp[name].record_stream(st)
-            if has_wgrad and on_branch is not None and not merge_adam:
-                # the colour grid and the colour decoder, on the weight-gradient branch after its kernel
-                # and after the lean launch (the colour grid's gradient; and no Adam may rewrite the grid
-                # while k_color_wgrad still gathers from it)
+                        gp[name].record_stream(st)  # (allocated on the caller's stream)
+            if plan.has_wgrad and on_branch is not None and not plan.merge_adam:
+                # colour update: the colour grid and decoder, on the weight-gradient branch after its kernel and
+                # the lean launch (no Adam may rewrite the grid while k_color_wgrad still gathers from it)
                 with torch.cuda.stream(wgrad_st):
                     wgrad_st.wait_event(self._lean_ev)
                     on_branch(["color"], part="all")
-            for st in used:
+            for st in streams[1:]:  # join
                 main.wait_stream(st)
             if on_pts is not None and pts_grad:
                 on_pts([gp[d] for d in decs])
-            if merged_names is not None:
-                # NSLAM_ADAM_ON=main: the merged update on the main stream after the join (the weight
-                # gradients ran on it; the join covers the lean launch), so the next iteration's forward
-                # follows it on the same queue
-                on_branch(merged_names, part="all")
         if not pts_grad:
             return None
-        parts = [gp[d] for d in decs]
-        if pts_parts:  # the per-decoder shares, for a consumer that sums them itself
-            return parts
-        out = parts[0]
-        for g in parts[1:]:
-            out += g
-        return out
+        parts = [gp[d] for d in decs]  # (pts_parts: the per-decoder shares, for a consumer that sums them itself)
+        return parts if pts_parts else functools.reduce(torch.Tensor.add_, parts)
+
+    # -- the backward's launches: each enqueues one unit of backward_plan on `st`, none schedules an update --
+    def _launch_wgrad(self, cfg, n, g_raw, st):
+        wsb = lib().nslam_query_bwd_decoder_workspace_size(ctypes.byref(cfg), _lib.DEC_COLOR, n)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=g_raw.device)
+        with ops._span("query_bwd.color_wgrad"):
+            rc = lib().nslam_color_wgrad(ctypes.byref(cfg), None, n, ptr(g_raw), ptr(ws), wsb, st.cuda_stream)
+        check(rc, "nslam_color_wgrad")
+
+    def _launch_lean(self, cfg, decs, names, n, g_raw, st, gp=None, live=None):
+        """gp: {decoder: its d/dpts buffer} (plain form); live: live_lists() of the batch (live-point form)."""
+        lc = _lib.NslamQueryCfg.from_buffer_copy(cfg)  # grids (and d/dpts) only
+        for name in names:
+            lc.dgrad[ops._DEC_ID[name]] = _lib.NslamDecGrad()
+        with ops._span("query_bwd." + "+".join(names)):
+            if live is not None:
+                ips, nps, mask = _live_tables(decs, names, *live)
+                rc = lib().nslam_query_bwd_decoders_live(ctypes.byref(lc), mask, None, n, ptr(g_raw), ips, nps,
+                                                         st.cuda_stream)
+            else:
+                gps, mask = _dec_table(names, lambda name: ptr(gp[name]) if gp else None)
+                rc = lib().nslam_query_bwd_decoders(ctypes.byref(lc), mask, None, n, ptr(g_raw), gps,
+                                                    st.cuda_stream)
+        check(rc, "nslam_query_bwd_decoders")
+
+    def _launch_one(self, cfg, name, n, g_raw, st, gp=None):
+        d = ops._DEC_ID[name]
+        wsb = lib().nslam_query_bwd_decoder_workspace_size(ctypes.byref(cfg), d, n)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=g_raw.device) if wsb else None
+        with ops._span("query_bwd." + name):
+            rc = lib().nslam_query_bwd_decoder(ctypes.byref(cfg), d, 0, None, n, ptr(g_raw),
+                                               ptr(gp[name]) if gp else None, ptr(ws), wsb, st.cuda_stream)
+        check(rc, "nslam_query_bwd_decoder")
 
     # -- one iteration ---------------------------------------------------------------------------
     def draws(self, seed, world=1, rank=0):
@@ -525,126 +588,48 @@ class MappingEngine:
                   world=1, rank=0, prefetch=False, post_bwd=None):
         """One mapping iteration; returns (ray_loss f64 [N], keep uint8 [N]) as device tensors.
 
-        frames: [(depth, color, c2w)] of the window; pix: int64 [len(frames)*n_per] randint
-        indices over the full image, or None: drawn in the gather kernel (ops.PixelDraws keyed by
-        `seed`, advanced on the device — no host RNG work per hipGraph replay; with world > 1 every
-        rank passes the same seed, gathers its slice of a global batch of n_per*world pixels per
-        frame and gets the global batch's max(gt_depth) from the gather kernel — no collective
-        before the sampler); hw = (H, W);
-        intrinsics = (fx, fy, cx, cy); n_kept: optional device int64 [1] += kept rays.
+        frames: [(depth, color, c2w)] of the window; pix: int64 [len(frames)*n_per] randint indices over the full
+        image, or None: drawn in the gather kernel (ops.PixelDraws keyed by `seed`, advanced on the device — no host
+        RNG work per hipGraph replay; with world > 1 every rank passes the same seed, gathers its slice of a global
+        batch of n_per*world pixels per frame and gets the global batch's max(gt_depth) from the gather kernel — no
+        collective before the sampler); hw = (H, W); intrinsics = (fx, fy, cx, cy); n_kept: optional device
+        int64 [1] += kept rays.
         gt_max: callable(gt_depth) → device scalar for a ray-sharded job (all-reduced max);
         allreduce: callable(list of grads) run before Adam (ray sharding, dense);
-        exchange: callable(grid keys, decoder names) run before Adam instead — the frustum-compacted
-        exchange (distributed.SparseGradExchange).
-        prefetch (device draws only): the pixel gather and sampler of the NEXT iteration run on a side
-        stream while this one renders and back-propagates — they depend only on the frames and the
-        device draw counter, not on the map.  Batches alternate between two persistent buffer sets
-        (self._parity), so a hipGraph of an even and one of an odd iteration replay alternately
-        with no copies.  Each call still draws, samples, renders and updates one batch; the first
-        call draws its own batch first.  The prefetched batch belongs to the frames of the call that
-        drew it: a call with other frames (another keyframe window, or poses changed in place, e.g.
-        by bundle adjustment — tracked by the tensors' identity and version counters) discards it
-        and draws its own batch.  With prefetch the returned `keep` is a persistent buffer, valid
-        until the next iteration() call (which overwrites it): clone it to keep it longer.
-        post_bwd(g_pts parts, rays_o, rays_d, z): the backward also forms d loss / d pts (every decoder's
-        share, a list of [N*S, 3] float64) and this runs as soon as they are written (on the mask-only
-        launch's stream, beside the weight gradients; query_bwd on_pts) — bundle adjustment's camera
-        gradients and camera step (Mapper.py:346-363, 503-504).  Its work must be ordered before the
-        next iteration by the join (it is: it runs on a stream the join covers).  Camera poses that a step changes in place make a prefetched batch
-        stale (the version check cannot see a kernel's writes): the caller passes prefetch=False whenever
-        its camera step can move them (Mapper: the colour stage, where their lr is not 0).
-        Live-point lists (self.live_points) ride with the batch and are formed again when a slot map was
-        rebound since (set_rows, bind_masks); a captured hipGraph of prefetching iterations replays the lists
-        of its capture-time ordering, so rebind rows only before a replay whose first iteration draws its
-        own batch (as Mapper.optimize_map's per-stage graphs do).
-        """
-        H, W = hw
-        fx, fy, cx, cy = intrinsics
+        exchange: callable(grid keys, decoder names) run before Adam instead — the frustum-compacted exchange
+        (distributed.SparseGradExchange).
+        prefetch (device draws only): the pixel gather and sampler of the NEXT iteration run on a side stream while
+        this one renders and back-propagates — they depend only on the frames and the device draw counter, not on
+        the map (PrefetchRing: when a prefetched batch is valid).  Each call still draws, samples, renders and
+        updates one batch; the first call draws its own batch first.  With prefetch the returned `keep` is a
+        persistent buffer, valid until the next iteration() call (which overwrites it): clone it to keep it longer.
+        post_bwd(g_pts parts, rays_o, rays_d, z): the backward also forms d loss / d pts (every decoder's share, a
+        list of [N*S, 3] float64) and this runs as soon as they are written (on the mask-only launch's stream,
+        beside the weight gradients; query_bwd on_pts) — bundle adjustment's camera gradients and camera step
+        (Mapper.py:346-363, 503-504).  Its work is ordered before the next iteration by the join (it runs on a
+        stream the join covers)."""
         keys, dnames = self.grads_for(stage, trainable_decoders)
         if exchange is not None and hasattr(exchange, "validate"):
             exchange.validate(self, keys, dnames)  # raises before anything of the iteration is enqueued
-        draw = self.draws(seed, world, rank) if pix is None else None
         # live-point lists: a mapping iteration without d/dpts whose grids (some of them) accumulate a
-        # frustum-compacted gradient; they ride with the ray batch (entries 6, 7 of a buffer set)
+        # frustum-compacted gradient; they ride with the ray batch
         use_live = (self.live_points and post_bwd is None and self.grid_grads and self.merge
                     and any(k in self.slot for k in keys))
-
-        def rays(out=None):  # pixels → rays + inside mask, then the sampler (Mapper.py:457-484, Renderer.py:82-174)
-            ro, rd, gd, gc, keep = ops.gather_rays(frames, pix, n_per, H, W, (0, H, 0, W), fx, fy, cx, cy,
-                                                   self.bound, draw=draw, n_kept=n_kept,
-                                                   out=None if out is None else out[:5])
-            gsamp = gd if (use_gt_in_sampler and stage != "coarse") else None
-            if gsamp is None:
-                gm = None
-            elif draw is not None and draw.gt_max is not None:  # global batch max from the gather kernel
-                gm = draw.gt_max
-            else:
-                gm = gt_max(gd) if gt_max is not None else None
-            z = ops.sample_z(ro, rd, gsamp, self.bound, self.n_strat, self.n_surf, self.lindisp, gt_max=gm,
-                             out=None if out is None else out[5])
-            lv = list(self.live_lists(stage, ro, rd, z, out=None if out is None else out[6:8])) if use_live else []
-            return [ro, rd, gd, gc, keep, z] + lv
-
-        prefetch = prefetch and pix is None
+        rays = functools.partial(self._rays, stage, frames, pix, n_per, hw, intrinsics, n_kept=n_kept, gt_max=gt_max,
+                                 draw=self.draws(seed, world, rank) if pix is None else None,
+                                 use_gt=use_gt_in_sampler, use_live=use_live)
         side = None
-        if prefetch:
-            # A prefetched batch is only valid for the very frames (images and poses, unmodified) it was
-            # gathered from: held by weak reference (identity — a new tensor that reuses a freed one's
-            # address is not the same frame) and version counter.
-            ftens = [t for f in frames for t in f]
-            pkey = (stage, n_per, hw, use_gt_in_sampler, seed, world, rank, use_live)
-            # live-point lists are valid for the slot maps they were formed from only: each buffer set
-            # remembers their generation (set_rows, bind_masks, Mapper._bind_frustum), and a set whose lists
-            # are older keeps its rays and gets new lists on the main stream before they are used
-            gen = (self.layout_gen, self.rows_gen)
-            valid = (self._pre is not None and self._pre[0] == pkey and len(self._pre[1]) == len(ftens)
-                     and all(r() is t and v == t._version for (r, v), t in zip(self._pre[1], ftens)))
-            if not valid:
-                first = rays()  # first call: this iteration's batch (set 0), then a same-shaped set 1
-                self._pre = (pkey, [(weakref.ref(t), t._version) for t in ftens],
-                             [first, [torch.empty_like(t) for t in first]])
-                self._parity = 0
-                self._live_gen = [gen, None]
-            par = self._parity
-            cur, nxt = self._pre[2][par], self._pre[2][1 - par]
-            self._parity ^= 1
-            if use_live and self._live_gen[par] != gen:
-                # (ordered after the side stream's writes of this set by the previous iteration's join)
-                self.live_lists(stage, cur[0], cur[1], cur[5], out=cur[6:8])
-                self._live_gen[par] = gen
-            main = torch.cuda.current_stream(self.device)
-            if self._pre_stream is None:
-                if self.prefetch_stream == "lean" and self.wgrad_first and self.concurrent:
-                    # the backward's first side stream (the mask-only launch's, with the weight-gradient
-                    # branch enqueued first on the main stream): one side queue fewer in the iteration's
-                    # graph; the prefetch is done long before that stream's backward work.  In any other
-                    # topology that side stream carries the weight-gradient branch: the prefetch gets its own
-                    if not self._side:
-                        self._side.append(torch.cuda.Stream(self.device))
-                    self._pre_stream = self._side[0]
-                else:
-                    self._pre_stream = torch.cuda.Stream(self.device)
-            side = self._pre_stream
-
-            def launch_prefetch():
-                side.wait_stream(main)  # the previous iteration's backward has released `nxt`
-                with torch.cuda.stream(side):
-                    rays(out=nxt)  # the next iteration's batch, beside this iteration's render + backward
-                self._live_gen[1 - par] = gen
-
-            if self.prefetch_at == "start":
-                launch_prefetch()
-            batch = cur
+        if prefetch and pix is None:
+            key = (stage, n_per, hw, use_gt_in_sampler, seed, world, rank, use_live)
+            batch, side = self._prefetched(rays, key, [t for f in frames for t in f], stage, use_live)
         else:
             batch = rays()
-        ro, rd, gd, gc, keep, z = batch[:6]
-        live = tuple(batch[6:8]) if use_live else None
+        ro, rd, z = batch.ro, batch.rd, batch.z
         mirror = hasattr(optimizer, "set_mirror")
         raw = self.query_fwd(stage, ro, rd, z, defer_occ=True, tape="color" in dnames)
-        if side is not None and self.prefetch_at != "start":
-            launch_prefetch()  # forks after the forward: beside the loss and the backward
-        _, _, _, ray_loss, g_raw = ops.render_loss(raw, z, gd, gc, keep, mode="mapper", use_color=stage == "color",
-                                                   w_color=self.w_color, occ_add=self.occ_add)
+        _, _, _, ray_loss, g_raw = ops.render_loss(raw, z, batch.gd, batch.gc, batch.keep, mode="mapper",
+                                                   use_color=stage == "color", w_color=self.w_color,
+                                                   occ_add=self.occ_add)
         if not self._clean:
             self.gall.zero_()  # grid and decoder gradients: one memset
         # Adam resets every gradient entry it reads.  With compact gradients for every grid of the
@@ -669,57 +654,77 @@ class MappingEngine:
             # launch the middle / fine grid rows, the weight-gradient branch (once the lean launch is
             # done too) the colour grid and the colour decoder — so no Adam waits for the whole backward
             def on_branch(names, part=None):  # the decoders of one launch: one Adam call for their grids
-                sub = {}                         # (part "grids" / "decoders": only those)
-                for name in names:
-                    if _GRID_OF[name] in keys and part != "decoders":
-                        sub[self.c[_GRID_OF[name]]] = grads[self.c[_GRID_OF[name]]]
-                    if name in dnames and part != "grids":
-                        sub[self.decs[name].param] = grads[self.decs[name].param]
+                params = [self.c[_GRID_OF[nm]] for nm in names if _GRID_OF[nm] in keys]
+                if part != "grids":  # ... and their own parameters
+                    params += [self.decs[nm].param for nm in names if nm in dnames]
+                sub = {p: grads[p] for p in params}
                 if sub:
                     optimizer.step(grads=sub, zero_grad=clean)
 
         on_pts = (lambda parts: post_bwd(parts, ro, rd, z)) if post_bwd is not None else None
         self.query_bwd(stage, ro, rd, z, g_raw, keys, dnames, on_branch=on_branch, ordered_branches=sharded,
-                       pts_grad=post_bwd is not None, pts_parts=True, on_pts=on_pts, live=live)
-        if sharded:
-            pass
-        elif exchange is not None:  # frustum-compacted all-reduce (distributed.SparseGradExchange)
+                       pts_grad=post_bwd is not None, pts_parts=True, on_pts=on_pts,
+                       live=batch.live if use_live else None)
+        if exchange is not None and not sharded:  # frustum-compacted all-reduce (distributed.SparseGradExchange)
             exchange(keys, dnames)
-        elif allreduce is not None:  # the grid gradients as one flat buffer, plus the decoder gradients
+        elif allreduce is not None and not sharded:  # the grid gradients as one flat buffer, plus the decoder gradients
             allreduce([self.gbuf] + [self.decs[n].grad for n in dnames])
         if side is not None:  # join: the next call reads the prefetched set
-            main.wait_stream(side)
+            torch.cuda.current_stream(self.device).wait_stream(side)
         if on_branch is None:
             optimizer.step(grads=grads, zero_grad=clean)
         self._clean = clean and (not sharded or exchange.leaves_clean)
         if not mirror:
             for n in dnames:
                 self.decs[n].repack()
-        return ray_loss, keep
+        return ray_loss, batch.keep
 
+    def _rays(self, stage, frames, pix, n_per, hw, intrinsics, *, draw, n_kept, gt_max, use_gt, use_live, out=None):
+        """The iteration's RayBatch (into `out` when given): pixels → rays + inside mask, then the sampler
+        (Mapper.py:457-484, Renderer.py:82-174), then the live-point lists, all on the current stream."""
+        H, W = hw
+        into = None if out is None else (out.ro, out.rd, out.gd, out.gc, out.keep)
+        ro, rd, gd, gc, keep = ops.gather_rays(frames, pix, n_per, H, W, (0, H, 0, W), *intrinsics, self.bound,
+                                               draw=draw, n_kept=n_kept, out=into)
+        gsamp = gd if (use_gt and stage != "coarse") else None
+        gm = None
+        if gsamp is not None and draw is not None and draw.gt_max is not None:
+            gm = draw.gt_max  # global batch max from the gather kernel
+        elif gsamp is not None and gt_max is not None:
+            gm = gt_max(gd)
+        z = ops.sample_z(ro, rd, gsamp, self.bound, self.n_strat, self.n_surf, self.lindisp, gt_max=gm,
+                         out=None if out is None else out.z)
+        if out is None:
+            out = RayBatch(ro, rd, gd, gc, keep, z)
+        if use_live:
+            out.live_idx, out.n_live = self.live_lists(stage, ro, rd, z, out=out.live)
+        return out
 
-def camera_dirs(pix, n_per, n_frames, window, intrinsics, device):
-    """Camera-frame ray directions of select_uv pixel draws (src/common.py:80-84, 113-134):
-    dirs = ((i-cx)/fx, -(j-cy)/fy, -1) for window index k -> (j, i) = (h0 + k // ww, w0 + k % ww)."""
-    h0, h1, w0, w1 = window
-    fx, fy, cx, cy = intrinsics
-    ww = w1 - w0
-    i = (pix % ww + w0).to(torch.float32)
-    j = (pix // ww + h0).to(torch.float32)
-    d = torch.stack([(i - cx) / fx, -(j - cy) / fy, -torch.ones_like(i)], -1)
-    return d.view(n_frames, n_per, 3)
+    def _prefetched(self, rays, key, ftens, stage, use_live):
+        """(this iteration's batch from the ring, the ring's side stream), after enqueuing the next one's there.
+        A ring of another key or other frames is started over: this call then draws its own batch first."""
+        ring = self.ring
+        gen = (self.layout_gen, self.rows_gen)
+        if not ring.valid_for(key, ftens):
+            ring.start(key, ftens, rays(), gen)
+            self._parity = 0
+        par = self._parity
+        cur, nxt = ring.current(par), ring.next(par)
+        self._parity ^= 1
+        if use_live and ring.live_gen[par] != gen:
+            # (ordered after the side stream's writes of this set by the previous iteration's join)
+            self.live_lists(stage, cur.ro, cur.rd, cur.z, out=cur.live)
+            ring.live_gen[par] = gen
+        side = ring.side_stream(self)
+        side.wait_stream(torch.cuda.current_stream(self.device))  # the previous iteration's backward has released `nxt`
+        with torch.cuda.stream(side):
+            rays(out=nxt)  # the next iteration's batch, beside this iteration's render + backward
+        ring.live_gen[1 - par] = gen
+        return cur, side
 
-
-def c2w_grads(g_pts, z, dirs):
-    """d loss / d c2w[:3, :4] per frame from d loss / d pts, through pts = o + d·z
-    (Renderer.py:172-174), rays_o = t and rays_d = R·dir (common.py:80-89):
-    g_t = sum_{r,s} g_pts, g_R = sum_r (sum_s z g_pts) dirᵀ.  dirs [F, n, 3] → [F, 3, 4]."""
-    F, n = dirs.shape[:2]
-    gp = g_pts.view(F, n, -1, 3)
-    g_ro = gp.sum(2).float()
-    g_rd = (gp * z.view(F, n, -1, 1)).sum(2).float()
-    g_R = torch.einsum("fnm,fnk->fmk", g_rd, dirs)
-    return torch.cat([g_R, g_ro.sum(1)[..., None]], 2)
+    def drop_prefetch(self):
+        """Forget the prefetched batch: the next prefetching iteration draws its own first."""
+        self.ring.drop()
 
 
 class TrackingEngine:
@@ -750,10 +755,7 @@ class TrackingEngine:
         self.window = (he, self.H - he, we, self.W - we)
         self.w_color, self.handle_dynamic, self.use_color = w_color, handle_dynamic, use_color
         self.device = torch.device(device)
-        # the iteration's persistent buffers, made on its first call: the pose, the camera gradient's workspace
-        # and ticket (nslam_cam_grad_parts) and the last iteration's loss (device f64 scalar, overwritten by
-        # the next one)
-        self._c2w = self._cam_ws = self._cam_ticket = self._loss = None
+        self._c2w = self._cam_ws = self._cam_ticket = self._loss = None  # (_buffers)
         # ABI v15 nslam_cam_grad_parts: the frozen decoders' d/dpts buffers summed inside a
         # multi-workgroup camera-gradient kernel (no torch adds, no single-workgroup reduction)
         self.cam_parts = True
@@ -789,55 +791,53 @@ class TrackingEngine:
         iteration).  Both live in the fused camera tail (nslam_cam_grad_step_lr2) only: with cam_tail or
         cam_parts off, or an optimizer the tail does not apply to, the call raises, it does not step with one
         rate."""
-        lr2 = lr_quat is not None or best_before_step
-        if lr2 and not (self.cam_parts and self.cam_tail and self._tail_ok(optimizer, cam)):
+        tail = self.cam_parts and self.cam_tail and self._tail_ok(optimizer, cam)
+        if (lr_quat is not None or best_before_step) and not tail:
             raise RuntimeError("TrackingEngine.iteration: lr_quat / best_before_step need the fused camera tail "
                                "(cam_parts and cam_tail on, a FusedAdam over the camera 7-vector alone)")
-        fx, fy, cx, cy = self.intr
         n = pix.numel() if pix is not None else int(n)
         draw = self.eng.draws(seed) if pix is None else None
-        if self._c2w is None:
-            self._c2w = torch.empty(3, 4, dtype=torch.float32, device=cam.device)
-            self._cam_ws = torch.zeros(ops.CAM_GRAD_WS_DOUBLES, dtype=torch.float64, device=cam.device)
-            self._cam_ticket = torch.zeros(1, dtype=torch.int32, device=cam.device)
-            self._loss = torch.empty((), dtype=torch.float64, device=cam.device)
-        # get_camera_from_tensor inside the gather (ABI v21), which also leaves the pose in self._c2w for
-        # the camera gradient
-        c2w = self._c2w
+        # get_camera_from_tensor inside the gather (ABI v21), which also leaves the pose in c2w for the
+        # camera gradient
+        c2w = self._buffers(cam)
         ro, rd, gd, gc, keep = ops.gather_rays([(depth, color, c2w, cam.detach())], pix, n, self.H, self.W,
-                                               self.window, fx, fy, cx, cy, self.bound, draw=draw)
+                                               self.window, *self.intr, self.bound, draw=draw)
         z = ops.sample_z(ro, rd, gd, self.bound, self.n_strat, self.n_surf)
         # the fine + middle occupancy sum is formed by the loss kernel as it reads raw (no combine pass)
         raw = self.eng.query_fwd("color", ro, rd, z, defer_occ=True)
         _, _, _, ray_loss, g_raw = ops.render_loss(raw, z, gd, gc, keep, mode="tracker", use_color=self.use_color,
                                                    handle_dynamic=self.handle_dynamic, w_color=self.w_color,
                                                    occ_add=self.eng.occ_add)
-        if cam.grad is None:
-            cam.grad = torch.empty_like(cam)
-        if self.cam_parts:  # the decoders' d/dpts shares summed inside the multi-workgroup cam_grad (ABI v15)
-            gps = self.eng.query_bwd("color", ro, rd, z, g_raw, (), (), pts_grad=True, pts_parts=True)
-            if self.cam_tail and self._tail_ok(optimizer, cam):
-                ex, ex2, stp = optimizer.state_of(cam)
-                adam = (ex, ex2, stp, optimizer.group_of(cam)["lr"], *optimizer.betas, optimizer.eps)
-                bl, bc = (None, None) if best is None else (best[0], best[1])
-                ops.cam_grad_step(cam.detach(), c2w, gps, z, rd, cam.grad, self._cam_ws, self._cam_ticket, adam,
-                                  ray_loss, self._loss, bl, bc, lr_quat=lr_quat,
-                                  best_before_step=best_before_step)
-                return self._loss
-            ops.cam_grad_parts(cam.detach(), c2w, gps, z, rd, cam.grad, self._cam_ws, self._cam_ticket)
-        else:
-            g_pts = self.eng.query_bwd("color", ro, rd, z, g_raw, (), (), pts_grad=True)
-            # the whole pts → rays → c2w → 7-vector chain in one launch
+        g_pts = self.eng.query_bwd("color", ro, rd, z, g_raw, (), (), pts_grad=True, pts_parts=self.cam_parts)
+        bl, bc = (None, None) if best is None else (best[0], best[1])
+        if tail:  # camera gradient, Adam step, loss sum and best pose in one launch (ABI v23)
+            ex, ex2, stp = optimizer.state_of(cam)
+            adam = (ex, ex2, stp, optimizer.group_of(cam)["lr"], *optimizer.betas, optimizer.eps)
+            ops.cam_grad_step(cam.detach(), c2w, g_pts, z, rd, cam.grad, self._cam_ws, self._cam_ticket, adam,
+                              ray_loss, self._loss, bl, bc, lr_quat=lr_quat, best_before_step=best_before_step)
+            return self._loss
+        elif self.cam_parts:  # the decoders' d/dpts shares summed inside the multi-workgroup cam_grad (ABI v15)
+            ops.cam_grad_parts(cam.detach(), c2w, g_pts, z, rd, cam.grad, self._cam_ws, self._cam_ticket)
+        else:  # the shares summed by torch; the whole pts → rays → c2w → 7-vector chain in one launch
             ops.cam_grad(cam.detach(), c2w, g_pts, z, rd, cam.grad)
         optimizer.step()
         # the loss of the pose before the step (its rays' losses) and, with `best`, the best-pose update in
         # one launch: the candidate is the 7-vector right after that step, as the reference keeps it
         # (optimize_cam_in_batch steps before Tracker.py:245-247 compares)
-        if best is None:
-            ops.loss_sum_best(ray_loss, self._loss)
-        else:
-            ops.loss_sum_best(ray_loss, self._loss, best[0], cam.detach(), best[1])
+        ops.loss_sum_best(ray_loss, self._loss, bl, cam.detach(), bc)
         return self._loss
+
+    def _buffers(self, cam):
+        """The pose buffer; with it, on the first call, the iteration's other persistent buffers: the camera
+        gradient's workspace and ticket, the loss (device f64 scalar, overwritten by the next call), cam.grad."""
+        if self._c2w is None:
+            self._c2w = torch.empty(3, 4, dtype=torch.float32, device=cam.device)
+            self._cam_ws = torch.zeros(ops.CAM_GRAD_WS_DOUBLES, dtype=torch.float64, device=cam.device)
+            self._cam_ticket = torch.zeros(1, dtype=torch.int32, device=cam.device)
+            self._loss = torch.empty((), dtype=torch.float64, device=cam.device)
+        if cam.grad is None:
+            cam.grad = torch.empty_like(cam)
+        return self._c2w
 
 
 def frustum_rows(mask_xyz: torch.Tensor) -> torch.Tensor:

@@ -551,7 +551,7 @@ class Mapper(object):
                 pix[s * n_per:(s + 1) * n_per] = _common.select_uv(ar, ar, n_per, ar, ar.view(-1, 1).expand(-1, 3),
                                                                    device=self.device, generator=self.generator)[0]
         # device draws: the next iteration's gather + sampler run beside this one's render and backward
-        # (engine prefetch); every run of one stage starts with its own batch (eng._pre reset), so a
+        # (engine prefetch); every run of one stage starts with its own batch (eng.drop_prefetch), so a
         # captured run holds its whole prefetch chain.  With BA the poses the rays come from move only in
         # the colour stage (the cameras' lr is 0 before it, Mapper.py:420-421: their Adam state advances,
         # the 7-vectors do not), so only colour-stage BA iterations draw their rays serially.
@@ -578,14 +578,14 @@ class Mapper(object):
         if win.ncam:
             win.cams_init()
         self._set_stage_lr(opt, win, stage, lr_factor, zero=True)
-        eng._pre = None
+        eng.drop_prefetch()
         self._fused_iteration(eng, opt, win, stage)
         self._set_stage_lr(opt, win, stage, lr_factor)
         losses = None
         if self.loss_history is not None:
             losses = torch.zeros(n, dtype=torch.float64, device=self.device)
         g = torch.cuda.CUDAGraph()
-        eng._pre = None
+        eng.drop_prefetch()
         with ops.capture(g):
             if first:
                 win.cams_init()
@@ -662,7 +662,7 @@ class Mapper(object):
             for stg, n in runs:
                 self.stage = stg
                 self._set_stage_lr(opt, win, stg, lr_factor)
-                eng._pre = None
+                eng.drop_prefetch()
                 for _ in range(n):
                     if self._iter_hook is not None:
                         self._iter_hook(joint_iter)

@@ -898,13 +898,13 @@ def test_engine_prefetch_discards_batch_of_other_frames(tiny):
     for f, (_, _, m) in enumerate(moved):
         m[:3, 3] += 0.05 * (f + 1)
     eng.iteration("color", moved, *args, seed=11, prefetch=True)   # another window: fresh batch (set 0)
-    ro = eng._pre[2][0][0].view(len(moved), 150, 3)
+    ro = eng.ring.current(0).ro.view(len(moved), 150, 3)
     for f, (_, _, m) in enumerate(moved):
         assert torch.equal(ro[f], m[:3, 3].expand(150, 3)), f
     with torch.no_grad():
         moved[0][2][:3, 3] += 0.01                                     # a pose updated in place
     eng.iteration("color", moved, *args, seed=11, prefetch=True)
-    ro = eng._pre[2][0][0].view(len(moved), 150, 3)
+    ro = eng.ring.current(0).ro.view(len(moved), 150, 3)
     assert torch.equal(ro[0], moved[0][2][:3, 3].expand(150, 3))
 
 

@@ -213,7 +213,7 @@ def test_live_lists_follow_row_rebinding(tiny):
         eng.iteration("color", frames, *args, seed=11, prefetch=True)
         torch.cuda.synchronize()
         if live:  # the second call used the prefetched rays with lists of the rows bound for it
-            assert eng._live_gen[0] == eng._live_gen[1] == (eng.layout_gen, eng.rows_gen)
+            assert eng.ring.live_gen[0] == eng.ring.live_gen[1] == (eng.layout_gen, eng.rows_gen)
         out[live] = ({k: c[k].detach().clone() for k in KEYS}, eng.decs["color"].param.detach().clone())
     for k in KEYS:
         err = rel_l2(out[True][0][k], out[False][0][k])

@@ -28,7 +28,7 @@ def main():
         g_raw = torch.randn(n, 4, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
         eng.query_fwd("color", r_o, r_d, zz)
         keys, dn = eng.grads_for("color", ("color",))
-        cfg = eng._cfg("color", r_o, r_d, zz, keys, dn)
+        cfg = eng._cfg("color", r_o, r_d, zz, keys, dn, masks=eng._saved, tape=eng._tape)
         row = []
         for name, d in (("mid", 1), ("fine", 2), ("col", 3)):
             wsb = L.nslam_query_bwd_decoder_workspace_size(ctypes.byref(cfg), d, n)
