@@ -172,8 +172,7 @@ __device__ __forceinline__ void cam_grad_parts_body(const CamPartsArgs& a, unsig
     }
   }
 #pragma unroll
-  for (int k = 0; k < 12; ++k)
-    for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+  for (int k = 0; k < 12; ++k) acc[k] = wave_sum(acc[k]);
   __shared__ double red[12][kCamThreads / 64];
   __shared__ float g_tail[7];
   float* const g_lds = a.has_tail ? g_tail : nullptr;

@@ -1,9 +1,13 @@
-// nslam_composite.hip — volume compositing (occupancy mode) on gfx950 and its backward.
+// nslam_composite.hip — volume compositing on gfx950 and its backward: one compositor, two alpha models.
 //
-// Replaces raw2outputs_nerf_color (src/common.py:204-245) with occupancy=True
-// (configs/nice_slam.yaml:5) and its autograd backward:
-//   alpha_k = sigmoid(10 raw_k[3]);  T_k = prod_{j<k} (1 - alpha_j + 1e-10);  w_k = alpha_k T_k
+// Replaces raw2outputs_nerf_color (src/common.py:204-245) and its autograd backward:
+//   T_k = prod_{j<k} (1 - alpha_j + 1e-10);  w_k = alpha_k T_k
 //   rgb = sum_k w_k raw_k[:3] (f32);  depth = sum_k w_k z_k (f64);  var = sum_k w_k (z_k-depth)^2 (f64)
+// load_sample, ray_fwd and ray_bwd state this once, templated on the model that forms alpha:
+//   Occupancy  occupancy=True (configs/nice_slam.yaml:5): alpha_k = sigmoid(10 raw_k[3])
+//   Density    occupancy=False (iMAP*, common.py:222-245): alpha_k = 1 - exp(-relu(raw_k[3]) dists_k)
+// The stand-alone kernels (k_composite_fwd / _bwd of either model) and the fused rendering loss
+// (k_render_loss, Occupancy) all composite through them.
 // One wave per ray, one lane per sample; the transmittance is a wave prefix product and the sums
 // are wave shuffle reductions.  Rays with more than 64 samples are processed in 64-sample chunks
 // with a carried transmittance.
@@ -16,16 +20,6 @@ namespace {
 
 constexpr int kMaxS = 256;  // 4 chunks
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sumd(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 // inclusive prefix product over lanes
 __device__ __forceinline__ float wave_prefix_prod(float v, int lane) {
 #pragma unroll
@@ -50,23 +44,92 @@ __device__ __forceinline__ float sigmoid10(float occ) {
   return 1.f / (1.f + expf(-x));
 }
 
-struct RaySample {
+__device__ __forceinline__ float ray_norm(const float* __restrict__ d) {
+  return sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+}
+
+// One sample of a ray: alpha, factor, exclusive transmittance, weight, and what its model keeps of alpha
+// for the backward (M::Extra; nothing for Occupancy).
+template <class M>
+struct RaySample : M::Extra {
   float a, f, T, w;
   f32x4 raw;
   double z;
 };
 
-// Fill chunk `c` of a ray: alpha, factor, exclusive transmittance, weight.  carry = T entering.
-// occ (may be NULL): the middle occupancy of a deferred-combine query, added to raw[...,3] in the
-// reference's operand order (fine + middle, decoder.py:331-334) — what k_occ_combine would store.
-__device__ __forceinline__ RaySample load_sample(const float* raw, const double* z, int S, int k, int lane,
-                                                 float& carry, const float* occ = nullptr) {
-  RaySample s;
+// An alpha model holds a ray's own state and four steps: combine() completes the loaded raw of sample k
+// (act: k < S), alpha() forms its alpha from raw / z, alpha_bwd() takes alpha's cotangent to that of raw[3],
+// store_ray_grad() ends a backward.
+struct Occupancy {
+  struct Extra {};
+  // the middle occupancy of a deferred-combine query (may be NULL), added to raw[...,3] in the reference's
+  // operand order (fine + middle, decoder.py:331-334) — what k_occ_combine would store
+  const float* occ;
+
+  // the stand-alone kernels' ray: nothing deferred
+  __device__ static Occupancy of_ray(const float*, float*, int64_t) { return Occupancy{nullptr}; }
+  __device__ __forceinline__ void combine(RaySample<Occupancy>& s, int k, bool act) const {
+    if (occ && act) s.raw[3] = s.raw[3] + occ[k];
+  }
+  __device__ __forceinline__ float alpha(RaySample<Occupancy>& s, const double*, int, int, bool act) const {
+    return act ? sigmoid10(s.raw[3]) : 0.f;
+  }
+  __device__ __forceinline__ float alpha_bwd(const RaySample<Occupancy>& s, float g_a, bool) const {
+    return ((g_a * (1.f - s.a)) * s.a) * 10.f;  // sigmoid_backward, then the 10*
+  }
+  __device__ __forceinline__ void store_ray_grad(int) const {}
+};
+
+// Volume density: dists_k = float(z_(k+1) - z_k) (last: 1e10), times |rays_d|.  Adds the gradient of rays_d
+// (through |rays_d|) to the backward.  One sample is refused by the entry points: the reference sizes the
+// trailing 1e10 from an empty slice of z differences and composites nothing.
+struct Density {
+  struct Extra {
+    float e, dist0, sig;  // e = exp(-sigma dist); dist0 = the z difference before the norm factor
+  };
+  const float* rd;    // this ray's direction
+  float* grd;         // and its gradient (may be NULL)
+  float norm, gnorm;  // |rays_d|; this lane's share of d/d|rays_d|
+
+  __device__ static Density of_ray(const float* rays_d, float* g_rays_d, int64_t ray) {
+    return Density{rays_d + ray * 3, g_rays_d ? g_rays_d + ray * 3 : nullptr, ray_norm(rays_d + ray * 3), 0.f};
+  }
+  __device__ __forceinline__ void combine(RaySample<Density>&, int, bool) const {}
+  __device__ __forceinline__ float alpha(RaySample<Density>& s, const double* z, int S, int k, bool act) const {
+    s.dist0 = (k < S - 1) ? (float)(z[k + 1] - s.z) : 1e10f;
+    const float dist = s.dist0 * norm;
+    s.sig = s.raw[3] > 0.f ? s.raw[3] : 0.f;
+    // the correctly rounded exponential of the float32 argument: the factors of a transparent ray are e itself,
+    // so a mean error of expf near 1 adds up linearly along a 256-sample transmittance product
+    s.e = act ? (float)exp(-(double)(s.sig * dist)) : 1.f;
+    return 1.f - s.e;
+  }
+  __device__ __forceinline__ float alpha_bwd(const RaySample<Density>& s, float g_a, bool act) {
+    const float g_u = g_a * s.e;  // alpha = 1 - exp(-u), u = sigma dist
+    const float dist = s.dist0 * norm;
+    const float g_sig = g_u * dist;
+    if (act) gnorm += (g_u * s.sig) * s.dist0;  // d/d|rays_d| through dist = dist0 |rays_d|
+    return s.raw[3] > 0.f ? g_sig : 0.f;
+  }
+  __device__ __forceinline__ void store_ray_grad(int lane) {
+    if (!grd) return;
+    gnorm = wave_sum(gnorm);
+    if (lane < 3) grd[lane] = gnorm * (rd[lane] / norm);
+  }
+};
+
+// Fill sample k of a ray (lane's sample of a chunk): alpha, factor, exclusive transmittance, weight.
+// carry = T entering the chunk.  (The model by value, here and in ray_fwd: through a reference k_render_loss<0>
+// and <2> took 3 and 6 more VGPRs and lost a wave per SIMD each.)
+template <class M>
+__device__ __forceinline__ RaySample<M> load_sample(const M model, const float* raw, const double* z, int S, int k,
+                                                    int lane, float& carry) {
+  RaySample<M> s;
   const bool act = k < S;
   s.raw = act ? *reinterpret_cast<const f32x4*>(raw + (size_t)k * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-  if (occ && act) s.raw[3] = s.raw[3] + occ[k];
+  model.combine(s, k, act);
   s.z = act ? z[k] : 0.0;
-  s.a = act ? sigmoid10(s.raw[3]) : 0.f;
+  s.a = model.alpha(s, z, S, k, act);
   s.f = act ? (1.f - s.a) + 1e-10f : 1.f;
   const float incl = wave_prefix_prod(s.f, lane);
   float excl = __shfl_up(incl, 1, 64);
@@ -77,57 +140,47 @@ __device__ __forceinline__ RaySample load_sample(const float* raw, const double*
   return s;
 }
 
-__global__ __launch_bounds__(256) void k_composite_fwd(const float* __restrict__ raw, const double* __restrict__ zv,
-                                                       int64_t n, int S, double* __restrict__ depth,
-                                                       double* __restrict__ var, float* __restrict__ color) {
-  const int lane = threadIdx.x & 63;
-  const int64_t ray = (int64_t)blockIdx.x * 4 + wave_id();
-  if (ray >= n) return;
-  const float* rr = raw + ray * (int64_t)S * 4;
-  const double* zz = zv + ray * (int64_t)S;
+// Forward of one ray (the wave owns it): loads all its samples (kept in registers for the stores or a
+// backward) and returns depth (float64), var (float64) and colour (float32 x3).
+struct RayOut {
+  double d, v;
+  float c0, c1, c2;
+};
+
+template <class M>
+__device__ __forceinline__ RayOut ray_fwd(const M model, const float* rr, const double* zz, int S, int nch,
+                                          RaySample<M> (&sm)[kMaxS / 64], int lane) {
   float carry = 1.f;
-  float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-  double d = 0.0;
-  const int nch = (S + 63) / 64;
-  float wk[kMaxS / 64];
-  double zk[kMaxS / 64];
+  RayOut o{0.0, 0.0, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int c = 0; c < kMaxS / 64; ++c) {
     if (c >= nch) break;
-    const RaySample s = load_sample(rr, zz, S, c * 64 + lane, lane, carry);
-    c0 += s.w * s.raw[0];
-    c1 += s.w * s.raw[1];
-    c2 += s.w * s.raw[2];
-    d += (double)s.w * s.z;
-    wk[c] = s.w;
-    zk[c] = s.z;
+    sm[c] = load_sample(model, rr, zz, S, c * 64 + lane, lane, carry);
+    o.c0 += sm[c].w * sm[c].raw[0];
+    o.c1 += sm[c].w * sm[c].raw[1];
+    o.c2 += sm[c].w * sm[c].raw[2];
+    o.d += (double)sm[c].w * sm[c].z;
   }
-  c0 = wave_sum(c0);
-  c1 = wave_sum(c1);
-  c2 = wave_sum(c2);
-  d = wave_sumd(d);
-  double v = 0.0;
+  o.c0 = wave_sum(o.c0);
+  o.c1 = wave_sum(o.c1);
+  o.c2 = wave_sum(o.c2);
+  o.d = wave_sum(o.d);
 #pragma unroll
   for (int c = 0; c < kMaxS / 64; ++c) {
     if (c >= nch) break;
-    const double dz = zk[c] - d;
-    v += ((double)wk[c] * dz) * dz;  // (weights*tmp)*tmp
+    const double dz = sm[c].z - o.d;
+    o.v += ((double)sm[c].w * dz) * dz;  // (weights*tmp)*tmp
   }
-  v = wave_sumd(v);
-  if (lane == 0) {
-    depth[ray] = d;
-    var[ray] = v;
-    color[ray * 3 + 0] = c0;
-    color[ray * 3 + 1] = c1;
-    color[ray * 3 + 2] = c2;
-  }
+  o.v = wave_sum(o.v);
+  return o;
 }
 
-// Backward of one ray (the wave owns it) given its loaded samples, depth and cotangents
-// (g_depth, g_var float64; g_color float32); writes g_raw for the ray's samples.
-__device__ __forceinline__ void ray_bwd(const RaySample (&sm)[kMaxS / 64], int nch, int S, double d, double gd,
-                                        double gv, float gc0, float gc1, float gc2, float* __restrict__ gr,
-                                        int lane) {
+// Backward of one ray given its loaded samples, depth and cotangents (g_depth, g_var float64; g_color
+// float32); writes g_raw for the ray's samples.
+template <class M>
+__device__ __forceinline__ void ray_bwd(M& model, const RaySample<M> (&sm)[kMaxS / 64], int nch, int S, double d,
+                                        double gd, double gv, float gc0, float gc1, float gc2,
+                                        float* __restrict__ gr, int lane) {
   // d var / d depth = -sum_k [gv*(w dz) + (gv dz) w]
   double sdep = 0.0;
 #pragma unroll
@@ -137,13 +190,13 @@ __device__ __forceinline__ void ray_bwd(const RaySample (&sm)[kMaxS / 64], int n
     const double w = (double)sm[c].w;
     sdep += gv * (w * dz) + (gv * dz) * w;
   }
-  const double gdepth = gd - wave_sumd(sdep);
+  const double gdepth = gd - wave_sum(sdep);
   // per-sample weight cotangent, then transmittance cotangent
   float gw[kMaxS / 64], gT[kMaxS / 64];
 #pragma unroll
   for (int c = 0; c < kMaxS / 64; ++c) {
     if (c >= nch) break;
-    const RaySample& s = sm[c];
+    const RaySample<M>& s = sm[c];
     const double dz = s.z - d;
     const float g_dep = (float)(gdepth * s.z);
     const float g_var = (float)((gv * dz) * dz);
@@ -156,87 +209,79 @@ __device__ __forceinline__ void ray_bwd(const RaySample (&sm)[kMaxS / 64], int n
 #pragma unroll
   for (int c = kMaxS / 64 - 1; c >= 0; --c) {
     if (c >= nch) continue;
-    const RaySample& s = sm[c];
+    const RaySample<M>& s = sm[c];
     const int k = c * 64 + lane;
     const float prod = (k < S) ? gT[c] * s.T : 0.f;
     const float incl = wave_suffix_sum(prod, lane);  // sum_{m>=k} within chunk
     const float nxt = __shfl_down(incl, 1, 64);
     const float R = (lane < 63 ? nxt : 0.f) + tail;  // sum_{m>k}
     tail += __shfl(incl, 0, 64);
-    const float g_f = R / s.f;                       // cumprod backward: reversed_cumsum(w*grad)/input
-    const float g_a = gw[c] * s.T - g_f;             // f = 1 - alpha + 1e-10
-    const float g_occ = ((g_a * (1.f - s.a)) * s.a) * 10.f;  // sigmoid_backward, then the 10*
+    const float g_f = R / s.f;            // cumprod backward: reversed_cumsum(w*grad)/input
+    const float g_a = gw[c] * s.T - g_f;  // f = 1 - alpha + 1e-10
+    const float g_x = model.alpha_bwd(s, g_a, k < S);
     if (k < S) {
       f32x4 o;
       o[0] = gc0 * s.w;
       o[1] = gc1 * s.w;
       o[2] = gc2 * s.w;
-      o[3] = g_occ;
+      o[3] = g_x;
       *reinterpret_cast<f32x4*>(gr + (int64_t)k * 4) = o;
     }
   }
 }
 
-// Forward of one ray: loads all its samples (kept in registers for a backward) and returns
-// depth (float64), var (float64) and colour (float32 x3) exactly as k_composite_fwd.
-struct RayOut {
-  double d, v;
-  float c0, c1, c2;
-};
-
-__device__ __forceinline__ RayOut ray_fwd(const float* rr, const double* zz, int S, int nch, RaySample (&sm)[kMaxS / 64],
-                                          int lane, const float* occ = nullptr) {
-  float carry = 1.f;
-  RayOut o{0.0, 0.0, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < kMaxS / 64; ++c) {
-    if (c >= nch) break;
-    sm[c] = load_sample(rr, zz, S, c * 64 + lane, lane, carry, occ);
-    o.c0 += sm[c].w * sm[c].raw[0];
-    o.c1 += sm[c].w * sm[c].raw[1];
-    o.c2 += sm[c].w * sm[c].raw[2];
-    o.d += (double)sm[c].w * sm[c].z;
-  }
-  o.c0 = wave_sum(o.c0);
-  o.c1 = wave_sum(o.c1);
-  o.c2 = wave_sum(o.c2);
-  o.d = wave_sumd(o.d);
-#pragma unroll
-  for (int c = 0; c < kMaxS / 64; ++c) {
-    if (c >= nch) break;
-    const double dz = sm[c].z - o.d;
-    o.v += ((double)sm[c].w * dz) * dz;  // (weights*tmp)*tmp
-  }
-  o.v = wave_sumd(o.v);
-  return o;
-}
-
-__global__ __launch_bounds__(256) void k_composite_bwd(const float* __restrict__ raw, const double* __restrict__ zv,
-                                                       int64_t n, int S, const double* __restrict__ gdep,
-                                                       const double* __restrict__ gvar,
-                                                       const float* __restrict__ gcol, float* __restrict__ graw) {
+// ray_fwd plus the stores.  rd: Density's rays_d; weights (may be NULL): its extra output for the sampler.
+template <class M>
+__global__ __launch_bounds__(256) void k_composite_fwd(const float* __restrict__ raw, const double* __restrict__ zv,
+                                                       const float* __restrict__ rd, int64_t n, int S,
+                                                       double* __restrict__ depth, double* __restrict__ var,
+                                                       float* __restrict__ color, float* __restrict__ weights) {
   const int lane = threadIdx.x & 63;
   const int64_t ray = (int64_t)blockIdx.x * 4 + wave_id();
   if (ray >= n) return;
-  const float* rr = raw + ray * (int64_t)S * 4;
-  const double* zz = zv + ray * (int64_t)S;
   const int nch = (S + 63) / 64;
-  RaySample sm[kMaxS / 64];
-  float carry = 1.f;
-  double d = 0.0;
+  RaySample<M> sm[kMaxS / 64];
+  const RayOut o = ray_fwd(M::of_ray(rd, nullptr, ray), raw + ray * (int64_t)S * 4, zv + ray * (int64_t)S, S, nch, sm,
+                           lane);
+  if (lane == 0) {
+    depth[ray] = o.d;
+    var[ray] = o.v;
+    color[ray * 3 + 0] = o.c0;
+    color[ray * 3 + 1] = o.c1;
+    color[ray * 3 + 2] = o.c2;
+  }
+  if (!weights) return;
 #pragma unroll
   for (int c = 0; c < kMaxS / 64; ++c) {
     if (c >= nch) break;
-    sm[c] = load_sample(rr, zz, S, c * 64 + lane, lane, carry);
-    d += (double)sm[c].w * sm[c].z;
+    const int k = c * 64 + lane;
+    if (k < S) weights[ray * (int64_t)S + k] = sm[c].w;
   }
-  d = wave_sumd(d);
+}
+
+// Loading (ray_fwd, of which only the depth is used: its colour and var sums are dead code here), the
+// cotangents (NULL: zero), ray_bwd.  rd / grd: Density's rays_d and its gradient (grd may be NULL).
+template <class M>
+__global__ __launch_bounds__(256) void k_composite_bwd(const float* __restrict__ raw, const double* __restrict__ zv,
+                                                       const float* __restrict__ rd, int64_t n, int S,
+                                                       const double* __restrict__ gdep,
+                                                       const double* __restrict__ gvar,
+                                                       const float* __restrict__ gcol, float* __restrict__ graw,
+                                                       float* __restrict__ grd) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ray = (int64_t)blockIdx.x * 4 + wave_id();
+  if (ray >= n) return;
+  const int nch = (S + 63) / 64;
+  M model = M::of_ray(rd, grd, ray);
+  RaySample<M> sm[kMaxS / 64];
+  const RayOut o = ray_fwd(model, raw + ray * (int64_t)S * 4, zv + ray * (int64_t)S, S, nch, sm, lane);
   const double gd = gdep ? gdep[ray] : 0.0;
   const double gv = gvar ? gvar[ray] : 0.0;
   const float gc0 = gcol ? gcol[ray * 3 + 0] : 0.f;
   const float gc1 = gcol ? gcol[ray * 3 + 1] : 0.f;
   const float gc2 = gcol ? gcol[ray * 3 + 2] : 0.f;
-  ray_bwd(sm, nch, S, d, gd, gv, gc0, gc1, gc2, graw + ray * (int64_t)S * 4, lane);
+  ray_bwd(model, sm, nch, S, o.d, gd, gv, gc0, gc1, gc2, graw + ray * (int64_t)S * 4, lane);
+  model.store_ray_grad(lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -357,8 +402,9 @@ __global__ __launch_bounds__(256) void k_render_loss(LossArgs a) {
   const float* rr = a.raw + ray * (int64_t)S * 4;
   const double* zz = a.z + ray * (int64_t)S;
   const int nch = (S + 63) / 64;
-  RaySample sm[kMaxS / 64];
-  const RayOut o = ray_fwd(rr, zz, S, nch, sm, lane, a.cfg.occ_add ? a.cfg.occ_add + ray * (int64_t)S : nullptr);
+  Occupancy model{a.cfg.occ_add ? a.cfg.occ_add + ray * (int64_t)S : nullptr};
+  RaySample<Occupancy> sm[kMaxS / 64];
+  const RayOut o = ray_fwd(model, rr, zz, S, nch, sm, lane);
   const bool kp = a.keep ? a.keep[ray] != 0 : true;
   const float gt = a.gt[ray];
   if (PASS != 2 && lane == 0) {
@@ -398,34 +444,68 @@ __global__ __launch_bounds__(256) void k_render_loss(LossArgs a) {
     lossd += (double)(w * ((fabsf(e0) + fabsf(e1)) + fabsf(e2)));
   }
   if (a.ray_loss && lane == 0) a.ray_loss[ray] = lossd;
-  if (a.g_raw) ray_bwd(sm, nch, S, o.d, gd, 0.0, gc0, gc1, gc2, a.g_raw + ray * (int64_t)S * 4, lane);
+  if (a.g_raw) ray_bwd(model, sm, nch, S, o.d, gd, 0.0, gc0, gc1, gc2, a.g_raw + ray * (int64_t)S * 4, lane);
+}
+
+// What the four compositor entry points check before they launch, in this order: the counts (min_samples: 2
+// for Density, see there), nothing to do, then the pointers.  True: launch; else *status is the answer.
+bool rays_to_launch(int64_t n_rays, int32_t n_samples, int min_samples, bool pointers_ok, int* status) {
+  if (n_rays < 0 || n_samples <= 0)
+    *status = NSLAM_EINVAL;
+  else if (n_samples > kMaxS || n_samples < min_samples)
+    *status = NSLAM_EUNSUPPORTED;
+  else if (n_rays == 0)
+    *status = NSLAM_OK;
+  else if (!pointers_ok)
+    *status = NSLAM_EINVAL;
+  else
+    return true;
+  return false;
+}
+
+// one wave per ray, four rays per workgroup
+template <class K, class... A>
+int launch_rays(K kernel, int64_t n_rays, void* stream, A... args) {
+  const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
+  hipLaunchKernelGGL(kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), args...);
+  return hip_status();
 }
 
 }  // namespace
 
 extern "C" int nslam_composite_fwd(const float* raw, const double* z_vals, int64_t n_rays, int32_t n_samples,
                                    double* depth, double* var, float* color, void* stream) {
-  if (n_rays < 0 || n_samples <= 0) return NSLAM_EINVAL;
-  if (n_samples > kMaxS) return NSLAM_EUNSUPPORTED;
-  if (n_rays == 0) return NSLAM_OK;
-  if (!raw || !z_vals || !depth || !var || !color) return NSLAM_EINVAL;
-  const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-  hipLaunchKernelGGL(k_composite_fwd, grid, block, 0, reinterpret_cast<hipStream_t>(stream), raw, z_vals, n_rays,
-                     (int)n_samples, depth, var, color);
-  return hip_status();
+  int status;
+  if (!rays_to_launch(n_rays, n_samples, 1, raw && z_vals && depth && var && color, &status)) return status;
+  return launch_rays(k_composite_fwd<Occupancy>, n_rays, stream, raw, z_vals, nullptr, n_rays, (int)n_samples, depth,
+                     var, color, nullptr);
 }
 
 extern "C" int nslam_composite_bwd(const float* raw, const double* z_vals, int64_t n_rays, int32_t n_samples,
                                    const double* g_depth, const double* g_var, const float* g_color, float* g_raw,
                                    void* stream) {
-  if (n_rays < 0 || n_samples <= 0) return NSLAM_EINVAL;
-  if (n_samples > kMaxS) return NSLAM_EUNSUPPORTED;
-  if (n_rays == 0) return NSLAM_OK;
-  if (!raw || !z_vals || !g_raw) return NSLAM_EINVAL;
-  const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-  hipLaunchKernelGGL(k_composite_bwd, grid, block, 0, reinterpret_cast<hipStream_t>(stream), raw, z_vals, n_rays,
-                     (int)n_samples, g_depth, g_var, g_color, g_raw);
-  return hip_status();
+  int status;
+  if (!rays_to_launch(n_rays, n_samples, 1, raw && z_vals && g_raw, &status)) return status;
+  return launch_rays(k_composite_bwd<Occupancy>, n_rays, stream, raw, z_vals, nullptr, n_rays, (int)n_samples,
+                     g_depth, g_var, g_color, g_raw, nullptr);
+}
+
+extern "C" int nslam_composite_density_fwd(const float* raw, const double* z_vals, const float* rays_d, int64_t n_rays,
+                                           int32_t n_samples, double* depth, double* var, float* color,
+                                           float* weights, void* stream) {
+  int status;
+  if (!rays_to_launch(n_rays, n_samples, 2, raw && z_vals && rays_d && depth && var && color, &status)) return status;
+  return launch_rays(k_composite_fwd<Density>, n_rays, stream, raw, z_vals, rays_d, n_rays, (int)n_samples, depth, var,
+                     color, weights);
+}
+
+extern "C" int nslam_composite_density_bwd(const float* raw, const double* z_vals, const float* rays_d, int64_t n_rays,
+                                           int32_t n_samples, const double* g_depth, const double* g_var,
+                                           const float* g_color, float* g_raw, float* g_rays_d, void* stream) {
+  int status;
+  if (!rays_to_launch(n_rays, n_samples, 2, raw && z_vals && rays_d && g_raw, &status)) return status;
+  return launch_rays(k_composite_bwd<Density>, n_rays, stream, raw, z_vals, rays_d, n_rays, (int)n_samples, g_depth,
+                     g_var, g_color, g_raw, g_rays_d);
 }
 
 namespace {
@@ -489,210 +569,5 @@ extern "C" int nslam_render_loss(const nslam_loss_cfg* cfg, const float* raw, co
     hipLaunchKernelGGL(k_median_thr, dim3(1), dim3(1024), lds, s, w, keep, (int)n_rays, w + n_rays);
   }
   hipLaunchKernelGGL(k_render_loss<2>, grid, block, 0, s, a);
-  return hip_status();
-}
-
-// ------------------------------------------------------------------------------------------
-// Volume-density compositing (iMAP*: occupancy=False, src/common.py:222-245) and its backward
-//   dists_k = float(z_(k+1) - z_k) (last: 1e10), times |rays_d|;  alpha_k = 1 - exp(-relu(sigma_k) dists_k)
-// then the transmittance product, rgb / depth / var of the occupancy kernel, plus the weights output.
-// One wave per ray, 64-sample chunks with a carried transmittance, as k_composite_fwd.
-// ------------------------------------------------------------------------------------------
-namespace {
-
-struct DSample {
-  float a, f, T, w, e, dist0, sig;  // e = exp(-sigma dist); dist0 = the z difference before the norm factor
-  f32x4 raw;
-  double z;
-};
-
-__device__ __forceinline__ float ray_norm(const float* __restrict__ d) {
-  return sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-}
-
-__device__ __forceinline__ DSample load_dsample(const float* raw, const double* z, int S, int k, int lane, float norm,
-                                                float& carry) {
-  DSample s;
-  const bool act = k < S;
-  s.raw = act ? *reinterpret_cast<const f32x4*>(raw + (size_t)k * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-  s.z = act ? z[k] : 0.0;
-  s.dist0 = (k < S - 1) ? (float)(z[k + 1] - s.z) : 1e10f;
-  const float dist = s.dist0 * norm;
-  s.sig = s.raw[3] > 0.f ? s.raw[3] : 0.f;
-  // the correctly rounded exponential of the float32 argument: the factors of a transparent ray are e itself,
-  // so a mean error of expf near 1 adds up linearly along a 256-sample transmittance product
-  s.e = act ? (float)exp(-(double)(s.sig * dist)) : 1.f;
-  s.a = 1.f - s.e;
-  s.f = act ? (1.f - s.a) + 1e-10f : 1.f;
-  const float incl = wave_prefix_prod(s.f, lane);
-  float excl = __shfl_up(incl, 1, 64);
-  if (lane == 0) excl = 1.f;
-  s.T = carry * excl;
-  s.w = s.a * s.T;
-  carry = carry * __shfl(incl, 63, 64);
-  return s;
-}
-
-__global__ __launch_bounds__(256) void k_composite_density_fwd(const float* __restrict__ raw,
-                                                               const double* __restrict__ zv,
-                                                               const float* __restrict__ rd, int64_t n, int S,
-                                                               double* __restrict__ depth, double* __restrict__ var,
-                                                               float* __restrict__ color, float* __restrict__ weights) {
-  const int lane = threadIdx.x & 63;
-  const int64_t ray = (int64_t)blockIdx.x * 4 + wave_id();
-  if (ray >= n) return;
-  const float* rr = raw + ray * (int64_t)S * 4;
-  const double* zz = zv + ray * (int64_t)S;
-  const float norm = ray_norm(rd + ray * 3);
-  float carry = 1.f;
-  float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-  double d = 0.0;
-  const int nch = (S + 63) / 64;
-  float wk[kMaxS / 64];
-  double zk[kMaxS / 64];
-#pragma unroll
-  for (int c = 0; c < kMaxS / 64; ++c) {
-    if (c >= nch) break;
-    const int k = c * 64 + lane;
-    const DSample s = load_dsample(rr, zz, S, k, lane, norm, carry);
-    c0 += s.w * s.raw[0];
-    c1 += s.w * s.raw[1];
-    c2 += s.w * s.raw[2];
-    d += (double)s.w * s.z;
-    wk[c] = s.w;
-    zk[c] = s.z;
-    if (weights && k < S) weights[ray * (int64_t)S + k] = s.w;
-  }
-  c0 = wave_sum(c0);
-  c1 = wave_sum(c1);
-  c2 = wave_sum(c2);
-  d = wave_sumd(d);
-  double v = 0.0;
-#pragma unroll
-  for (int c = 0; c < kMaxS / 64; ++c) {
-    if (c >= nch) break;
-    const double dz = zk[c] - d;
-    v += ((double)wk[c] * dz) * dz;
-  }
-  v = wave_sumd(v);
-  if (lane == 0) {
-    depth[ray] = d;
-    var[ray] = v;
-    color[ray * 3 + 0] = c0;
-    color[ray * 3 + 1] = c1;
-    color[ray * 3 + 2] = c2;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_composite_density_bwd(const float* __restrict__ raw,
-                                                               const double* __restrict__ zv,
-                                                               const float* __restrict__ rd, int64_t n, int S,
-                                                               const double* __restrict__ gdep,
-                                                               const double* __restrict__ gvar,
-                                                               const float* __restrict__ gcol, float* __restrict__ graw,
-                                                               float* __restrict__ grd) {
-  const int lane = threadIdx.x & 63;
-  const int64_t ray = (int64_t)blockIdx.x * 4 + wave_id();
-  if (ray >= n) return;
-  const float* rr = raw + ray * (int64_t)S * 4;
-  const double* zz = zv + ray * (int64_t)S;
-  float* gr = graw + ray * (int64_t)S * 4;
-  const float norm = ray_norm(rd + ray * 3);
-  const int nch = (S + 63) / 64;
-  DSample sm[kMaxS / 64];
-  float carry = 1.f;
-  double d = 0.0;
-#pragma unroll
-  for (int c = 0; c < kMaxS / 64; ++c) {
-    if (c >= nch) break;
-    sm[c] = load_dsample(rr, zz, S, c * 64 + lane, lane, norm, carry);
-    d += (double)sm[c].w * sm[c].z;
-  }
-  d = wave_sumd(d);
-  const double gd = gdep ? gdep[ray] : 0.0;
-  const double gv = gvar ? gvar[ray] : 0.0;
-  const float gc0 = gcol ? gcol[ray * 3 + 0] : 0.f;
-  const float gc1 = gcol ? gcol[ray * 3 + 1] : 0.f;
-  const float gc2 = gcol ? gcol[ray * 3 + 2] : 0.f;
-  double sdep = 0.0;
-#pragma unroll
-  for (int c = 0; c < kMaxS / 64; ++c) {
-    if (c >= nch) break;
-    const double dz = sm[c].z - d;
-    const double w = (double)sm[c].w;
-    sdep += gv * (w * dz) + (gv * dz) * w;
-  }
-  const double gdepth = gd - wave_sumd(sdep);
-  float gw[kMaxS / 64], gT[kMaxS / 64];
-#pragma unroll
-  for (int c = 0; c < kMaxS / 64; ++c) {
-    if (c >= nch) break;
-    const DSample& s = sm[c];
-    const double dz = s.z - d;
-    const float g_dep = (float)(gdepth * s.z);
-    const float g_var = (float)((gv * dz) * dz);
-    const float g_rgb = gc0 * s.raw[0] + gc1 * s.raw[1] + gc2 * s.raw[2];
-    gw[c] = (g_rgb + g_dep) + g_var;
-    gT[c] = gw[c] * s.a;
-  }
-  float tail = 0.f, gnorm = 0.f;
-#pragma unroll
-  for (int c = kMaxS / 64 - 1; c >= 0; --c) {
-    if (c >= nch) continue;
-    const DSample& s = sm[c];
-    const int k = c * 64 + lane;
-    const float prod = (k < S) ? gT[c] * s.T : 0.f;
-    const float incl = wave_suffix_sum(prod, lane);
-    const float nxt = __shfl_down(incl, 1, 64);
-    const float R = (lane < 63 ? nxt : 0.f) + tail;
-    tail += __shfl(incl, 0, 64);
-    const float g_f = R / s.f;
-    const float g_a = gw[c] * s.T - g_f;   // f = 1 - alpha + 1e-10
-    const float g_u = g_a * s.e;           // alpha = 1 - exp(-u), u = sigma dist
-    const float dist = s.dist0 * norm;
-    const float g_sig = g_u * dist;
-    if (k < S) {
-      gnorm += (g_u * s.sig) * s.dist0;    // d/d|rays_d| through dist = dist0 |rays_d|
-      f32x4 o;
-      o[0] = gc0 * s.w;
-      o[1] = gc1 * s.w;
-      o[2] = gc2 * s.w;
-      o[3] = s.raw[3] > 0.f ? g_sig : 0.f;
-      *reinterpret_cast<f32x4*>(gr + (int64_t)k * 4) = o;
-    }
-  }
-  if (grd) {
-    gnorm = wave_sum(gnorm);
-    if (lane < 3) grd[ray * 3 + lane] = gnorm * (rd[ray * 3 + lane] / norm);
-  }
-}
-
-}  // namespace
-
-extern "C" int nslam_composite_density_fwd(const float* raw, const double* z_vals, const float* rays_d, int64_t n_rays,
-                                           int32_t n_samples, double* depth, double* var, float* color,
-                                           float* weights, void* stream) {
-  if (n_rays < 0 || n_samples <= 0) return NSLAM_EINVAL;
-  // one sample: the reference sizes the trailing 1e10 from an empty slice of z differences and composites nothing
-  if (n_samples > kMaxS || n_samples < 2) return NSLAM_EUNSUPPORTED;
-  if (n_rays == 0) return NSLAM_OK;
-  if (!raw || !z_vals || !rays_d || !depth || !var || !color) return NSLAM_EINVAL;
-  const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-  hipLaunchKernelGGL(k_composite_density_fwd, grid, block, 0, reinterpret_cast<hipStream_t>(stream), raw, z_vals,
-                     rays_d, n_rays, (int)n_samples, depth, var, color, weights);
-  return hip_status();
-}
-
-extern "C" int nslam_composite_density_bwd(const float* raw, const double* z_vals, const float* rays_d, int64_t n_rays,
-                                           int32_t n_samples, const double* g_depth, const double* g_var,
-                                           const float* g_color, float* g_raw, float* g_rays_d, void* stream) {
-  if (n_rays < 0 || n_samples <= 0) return NSLAM_EINVAL;
-  // one sample: the reference sizes the trailing 1e10 from an empty slice of z differences and composites nothing
-  if (n_samples > kMaxS || n_samples < 2) return NSLAM_EUNSUPPORTED;
-  if (n_rays == 0) return NSLAM_OK;
-  if (!raw || !z_vals || !rays_d || !g_raw) return NSLAM_EINVAL;
-  const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-  hipLaunchKernelGGL(k_composite_density_bwd, grid, block, 0, reinterpret_cast<hipStream_t>(stream), raw, z_vals,
-                     rays_d, n_rays, (int)n_samples, g_depth, g_var, g_color, g_raw, g_rays_d);
   return hip_status();
 }

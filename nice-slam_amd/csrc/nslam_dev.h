@@ -97,6 +97,20 @@ __device__ __forceinline__ float fkey_inv(uint32_t k) {
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
 __device__ __forceinline__ int fidx(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
+// Wave reductions to every lane: the xor butterfly 32, 16, .. 1 (float or double sum; uint32_t max).  Every
+// lane adds in the same order, so all 64 hold the same bits.
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t m) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+  return m;
+}
+
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }

@@ -75,8 +75,7 @@ __global__ __launch_bounds__(kFrThreads) void k_frustum_depth(FrustumArgs a) {
     a.dws[i] = d;
   }
   // block max of the (non-negative) depths, one atomic per wave
-  uint32_t m = __float_as_uint(fmaxf(d, 0.f));
-  for (int off = 32; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off, 64));
+  const uint32_t m = wave_max_u32(__float_as_uint(fmaxf(d, 0.f)));
   if ((threadIdx.x & 63) == 0 && m) atomicMax(a.dmax, m);
 }
 

@@ -145,8 +145,7 @@ __global__ __launch_bounds__(256) void k_gather_rays(GatherArgs a) {
     if (lane == 0) wred[0][wv] = (uint32_t)cnt;
   }
   if (a.draw.gt_max) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) mkey = max(mkey, (uint32_t)__shfl_xor((int)mkey, d, 64));
+    mkey = wave_max_u32(mkey);
     if (lane == 0) wred[1][wv] = mkey;
   }
   __syncthreads();

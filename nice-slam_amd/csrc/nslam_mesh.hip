@@ -79,8 +79,8 @@ __device__ __forceinline__ float sample_depth(const float* __restrict__ img, int
 }
 
 __device__ __forceinline__ void wave_atomic_max(uint32_t* dst, float d) {
-  uint32_t m = __float_as_uint(fmaxf(d, 0.f));  // samples are >= 0: the bit pattern orders like the value
-  for (int off = 32; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off, 64));
+  // samples are >= 0: the bit pattern orders like the value
+  const uint32_t m = wave_max_u32(__float_as_uint(fmaxf(d, 0.f)));
   if ((threadIdx.x & 63) == 0 && m) atomicMax(dst, m);
 }
 
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(kMeshThreads) void k_face_area(const double* verts,
   // faces in cell order mostly share their wave's component: one atomic per wave then, else one per face
   const int32_t l0 = __shfl(l, 0, 64);
   if (__ballot(l != l0 && l >= 0) == 0 && l0 >= 0) {
-    for (int off = 32; off > 0; off >>= 1) ar += __shfl_xor(ar, off, 64);
+    ar = wave_sum(ar);
     if ((threadIdx.x & 63) == 0) atomicAdd(area + l0, ar);
   } else if (l >= 0) {
     atomicAdd(area + l, ar);

@@ -23,8 +23,7 @@ __global__ __launch_bounds__(256) void k_max_gt(const float* __restrict__ gt, in
   uint32_t m = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     m = max(m, fkey(gt[i]));
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+  m = wave_max_u32(m);
   if ((threadIdx.x & 63) == 0 && m) atomicMax(ws, m);
 }
 
@@ -134,8 +133,7 @@ __global__ __launch_bounds__(256) void k_sample_wave(SamplerArgs a) {
   if (a.local_max) {  // workgroup-wide max over the batch (all threads take part before any exit)
     uint32_t m = 0;
     for (int64_t i = threadIdx.x; i < a.n; i += 256) m = max(m, fkey(a.gt[i]));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+    m = wave_max_u32(m);
     if (lane == 0) wmax[wave_id()] = m;
     __syncthreads();
   }

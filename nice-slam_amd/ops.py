@@ -440,42 +440,63 @@ def query_decoder(dec, p, c_grid):
 # ----------------------------------------------------------------------------------------------
 # compositing
 # ----------------------------------------------------------------------------------------------
+def _composite_call(which, raw, z, rd, tensors, last):
+    """nslam_composite_<which>, or with rays_d nslam_composite_density_<which>: the same arguments plus rays_d
+    after z and one more tensor (`last`) before the stream."""
+    name = f"composite_{which}" if rd is None else f"composite_density_{which}"
+    n, s = z.shape
+    rays, extra = ((), ()) if rd is None else ((ptr(rd),), (ptr(last),))
+    with _span(name):
+        rc = getattr(lib(), "nslam_" + name)(ptr(raw), ptr(z), *rays, n, s, *(ptr(t) for t in tensors), *extra,
+                                             stream_ptr(raw.device))
+    check(rc, "nslam_" + name)
+
+
 class _Composite(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, raw, z):
-        raw = raw.detach().float().contiguous()
-        z = z.detach().double().contiguous()
-        n, s = z.shape
-        depth = torch.empty(n, dtype=torch.float64, device=raw.device)
-        var = torch.empty(n, dtype=torch.float64, device=raw.device)
-        color = torch.empty(n, 3, dtype=torch.float32, device=raw.device)
-        if n:
-            with _span("composite_fwd"):
-                rc = lib().nslam_composite_fwd(ptr(raw), ptr(z), n, s, ptr(depth), ptr(var), ptr(color),
-                                               stream_ptr(raw.device))
-            check(rc, "nslam_composite_fwd")
-        ctx.save_for_backward(raw, z)
-        return depth, var, color
+    """The ray compositor: occupancy mode (rays_d None), or volume density with rays_d [N,3], which adds the
+    non-differentiable weights output and the gradient of rays_d."""
 
     @staticmethod
-    def backward(ctx, gd, gv, gc):
-        raw, z = ctx.saved_tensors
+    def forward(ctx, raw, z, rays_d):
+        raw = raw.detach().float().contiguous()
+        z = z.detach().double().contiguous()
+        rd = rays_d.detach().float().contiguous() if rays_d is not None else None
         n, s = z.shape
-        g_raw = torch.empty_like(raw)
+        dev = raw.device
+        depth = torch.empty(n, dtype=torch.float64, device=dev)
+        var = torch.empty(n, dtype=torch.float64, device=dev)
+        color = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        weights = torch.empty(n, s, dtype=torch.float32, device=dev) if rd is not None else None
         if n:
+            _composite_call("fwd", raw, z, rd, (depth, var, color), weights)
+        ctx.save_for_backward(raw, z, rd)
+        if rd is None:
+            return depth, var, color
+        ctx.mark_non_differentiable(weights)
+        return depth, var, color, weights
+
+    @staticmethod
+    def backward(ctx, gd, gv, gc, _gw=None):
+        raw, z, rd = ctx.saved_tensors
+        g_raw = torch.empty_like(raw)
+        g_rd = torch.zeros_like(rd) if rd is not None and ctx.needs_input_grad[2] else None
+        if z.shape[0]:
             gd = gd.contiguous().double() if gd is not None else None
             gv = gv.contiguous().double() if gv is not None else None
             gc = gc.contiguous().float() if gc is not None else None
-            with _span("composite_bwd"):
-                rc = lib().nslam_composite_bwd(ptr(raw), ptr(z), n, s, ptr(gd), ptr(gv), ptr(gc), ptr(g_raw),
-                                               stream_ptr(raw.device))
-            check(rc, "nslam_composite_bwd")
-        return g_raw, None
+            _composite_call("bwd", raw, z, rd, (gd, gv, gc, g_raw), g_rd)
+        return g_raw, None, g_rd
 
 
 def composite(raw, z):
     """(depth f64 [N], var f64 [N], color f32 [N,3]) from raw [N,S,4] f32, z [N,S] f64."""
-    return _Composite.apply(raw, z)
+    return _Composite.apply(raw, z, None)
+
+
+def composite_density(raw, z, rays_d):
+    """(depth f64 [N], var f64 [N], color f32 [N,3], weights f32 [N,S]) of raw2outputs_nerf_color(occupancy=False);
+    differentiable in raw and rays_d (the |rays_d| factor of dists); weights is for the sampler (no gradient)."""
+    return _Composite.apply(raw, z, rays_d)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1598,50 +1619,6 @@ def imap_query_rays(params, rays_o, rays_d, z, oob_bound=None):
     with torch.no_grad():
         return _ImapQuery.apply(None if oob_bound is None else _bound_list(oob_bound), (rays_o, rays_d, z), None,
                                 *params)
-
-
-class _CompositeDensity(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, raw, z, rays_d):
-        raw = raw.detach().float().contiguous()
-        z = z.detach().double().contiguous()
-        rd = rays_d.detach().float().contiguous()
-        n, s = z.shape
-        dev = raw.device
-        depth = torch.empty(n, dtype=torch.float64, device=dev)
-        var = torch.empty(n, dtype=torch.float64, device=dev)
-        color = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        weights = torch.empty(n, s, dtype=torch.float32, device=dev)
-        if n:
-            with _span("composite_density_fwd"):
-                rc = lib().nslam_composite_density_fwd(ptr(raw), ptr(z), ptr(rd), n, s, ptr(depth), ptr(var),
-                                                       ptr(color), ptr(weights), stream_ptr(dev))
-            check(rc, "nslam_composite_density_fwd")
-        ctx.save_for_backward(raw, z, rd)
-        ctx.mark_non_differentiable(weights)
-        return depth, var, color, weights
-
-    @staticmethod
-    def backward(ctx, gd, gv, gc, _gw):
-        raw, z, rd = ctx.saved_tensors
-        n, s = z.shape
-        g_raw = torch.empty_like(raw)
-        g_rd = torch.zeros_like(rd) if ctx.needs_input_grad[2] else None
-        if n:
-            gd = gd.contiguous().double() if gd is not None else None
-            gv = gv.contiguous().double() if gv is not None else None
-            gc = gc.contiguous().float() if gc is not None else None
-            with _span("composite_density_bwd"):
-                rc = lib().nslam_composite_density_bwd(ptr(raw), ptr(z), ptr(rd), n, s, ptr(gd), ptr(gv), ptr(gc),
-                                                       ptr(g_raw), ptr(g_rd), stream_ptr(raw.device))
-            check(rc, "nslam_composite_density_bwd")
-        return g_raw, None, g_rd
-
-
-def composite_density(raw, z, rays_d):
-    """(depth f64 [N], var f64 [N], color f32 [N,3], weights f32 [N,S]) of raw2outputs_nerf_color(occupancy=False);
-    differentiable in raw and rays_d (the |rays_d| factor of dists); weights is for the sampler (no gradient)."""
-    return _CompositeDensity.apply(raw, z, rays_d)
 
 
 def sample_importance(z, weights, n_importance, merged=True):
