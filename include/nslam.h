@@ -543,8 +543,9 @@ int nslam_mesh_select(const int32_t* faces, int64_t n_faces, const int32_t* labe
 int nslam_mesh_remap(const int32_t* faces, int64_t n_faces, const int32_t* new_id, int32_t* out, void* stream);
 
 /* Evaluation (src/tools/cull_mesh.py, src/tools/eval_recon.py; csrc/nslam_eval.hip); additive, no ABI bump.
- * No entry point here uses atomics, with one exception: nslam_raster_depth combines its hits with an integer
- * atomicMin, which does not depend on the order.  Every output is the same from run to run.
+ * No entry point here uses atomics, with one exception: nslam_raster_depth (and the replay's nslam_scene_render on
+ * the same passes) combines its hits with an integer atomicMin, which does not depend on the order.  Every output
+ * is the same from run to run.
  *
  * seen[i] = 1 when vertex i (float64 [n][3], cast to float32 as the reference does) projects into the image
  * of any of n_frames cameras (cull_mesh.py:47-71, eval_recon.py:62-88).  w2c: device float32 [n_frames][16],
@@ -635,6 +636,50 @@ int nslam_raster_depth(const double* verts, int64_t n_verts, const int32_t* face
                        double cy, double z_near, double z_far, int64_t small_max_pixels, int32_t passes,
                        float* depth, void* ws, size_t ws_bytes, void* stream);
 size_t nslam_raster_workspace_size(int64_t capacity);
+
+/* The frames of visualizer.py (src/tools/viz.py, in place of its open3d window; csrc/nslam_raster.hip); additive.
+ * color uint8 [n_views][H][W][3]: a triangle mesh with vertex colours under a head light, and a set of points
+ * drawn as depth-tested square sprites, seen from nslam_raster_depth's cameras (w2c, fx, fy, cx, cy, z_near,
+ * z_far and the pixel-centre rays are that entry's).  depth float32 [n_views][H][W] (camera-space z of what the
+ * pixel shows, 0 for background) and ids int32 [n_views][H][W] (a face index; -2 - the point's index; -1 for
+ * background) are written when not NULL.
+ * Mesh: verts float64 [n_verts][3], faces int32 [n_faces][3], vert_colors uint8 [n_verts][3] (NULL: every vertex
+ * has the HOST colour grey[3]), normals [n_verts][3] unit vectors, float64 when normals_f64 else float32.
+ * Points: points float64 [n_points][3], point_colors uint8 [n_points][3], point_size the sprite's edge in pixels.
+ * Visibility: every hit is the 64-bit key (float32 bits of z) << 32 | id, id = the face's index or
+ * 0x80000000 | the point's index, combined per pixel with a 64-bit unsigned atomicMin: the nearest hit wins and
+ * at equal float32 z the lowest id, so a face beats a point.  Min does not depend on the order: the three
+ * images are bit-identical from run to run, for every small_max_pixels and every workspace size.  Faces take
+ * nslam_raster_depth's passes and arithmetic (with cull NONE and no points, depth has that entry's bits).
+ * cull, by the sign of the edge-function sum d . ((b - a) x (c - a)) of the ray direction d: NONE draws both
+ * sides, BACK drops the hits with a positive sum (the right-hand normal points away from the camera), FRONT
+ * those with a negative one.
+ * A point that is non-finite or whose camera z is not in (z_near, z_far] is dropped; otherwise, projected to
+ * (px, py), it covers the pixel centres (x, y) with px - s/2 <= x < px + s/2 and py - s/2 <= y < py + s/2
+ * inside the image, all at the point's z.  One thread per (point, view).
+ * RESOLVE, one thread per pixel: a point's pixel gets the point's colour; a face's pixel recomputes the face's
+ * edge functions there, which over their sum are the barycentrics of the hit, interpolates the vertex colours
+ * and normals and writes floor(colour * (ambient + (1 - ambient) * |n . d|) + 0.5) per channel, n the normalised
+ * interpolated normal (zero length: |n . d| = 1) and d the unit ray direction, both in the world frame; float64
+ * without FMA contraction.  Every other pixel gets the HOST colour background[3].
+ * Passes: nslam_raster_depth's CLEAR, SMALL, BIG and RESOLVE on the key image, and NSLAM_SCENE_POINTS between
+ * BIG and RESOLVE; NSLAM_SCENE_ALL runs all five.  The workspace holds the list and one key per pixel; its
+ * size function gives the bytes for a list of `capacity` items (at least 1) and n_views images of H x W.
+ * n_faces == 0 (NULL mesh) draws the points, n_points == 0 (NULL point set) the mesh, both zero clear to the
+ * background; n_views == 0: NSLAM_OK without a launch.  NSLAM_EINVAL: nslam_raster_depth's conditions, a cull
+ * mode or passes outside the enums, ambient outside [0, 1], point_size not positive, a NULL background, a NULL
+ * pointer of a non-empty mesh or point set, a workspace shorter than that of one item.  NSLAM_EUNSUPPORTED:
+ * point_size above 64, more than 65535 views in one call. */
+enum { NSLAM_CULL_NONE = 0, NSLAM_CULL_BACK = 1, NSLAM_CULL_FRONT = 2 };
+enum { NSLAM_SCENE_POINTS = 16, NSLAM_SCENE_ALL = 31 };
+int nslam_scene_render(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                       const uint8_t* vert_colors, const void* normals, int32_t normals_f64, const uint8_t grey[3],
+                       const double* points, const uint8_t* point_colors, int64_t n_points, double point_size,
+                       const double* w2c, int32_t n_views, int32_t H, int32_t W, double fx, double fy, double cx,
+                       double cy, double z_near, double z_far, int32_t cull, const uint8_t background[3],
+                       double ambient, int64_t small_max_pixels, int32_t passes, uint8_t* color, float* depth,
+                       int32_t* ids, void* ws, size_t ws_bytes, void* stream);
+size_t nslam_scene_workspace_size(int64_t capacity, int32_t n_views, int32_t H, int32_t W);
 
 /* Lens undistortion of a frame's colour image (src/utils/datasets.py:85-88, the TUM-RGBD configs; additive,
  * csrc/nslam_image.hip): dst = cv2.undistort(src, K, dist) with its defaults — the new camera matrix is K,

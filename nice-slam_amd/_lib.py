@@ -165,6 +165,8 @@ EXPORTS = (
     "nslam_composite_density_bwd", "nslam_sample_importance",
     # the visualiser's panel mosaic (additive: no ABI bump)
     "nslam_vis_panels",
+    # replay: the scene renderer of visualizer.py's frames (additive: no ABI bump)
+    "nslam_scene_render", "nslam_scene_workspace_size",
 )
 
 _lib = None
@@ -289,6 +291,11 @@ def lib():
         L.nslam_composite_density_bwd.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
         L.nslam_sample_importance.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
         L.nslam_vis_panels.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
+        u8x3 = ctypes.POINTER(ctypes.c_uint8)
+        L.nslam_scene_render.argtypes = [vp, i64, vp, i64, vp, vp, i32, u8x3, vp, vp, i64, f64, vp, i32, i32, i32, f64,
+                                         f64, f64, f64, f64, f64, i32, u8x3, f64, i64, i32, vp, vp, vp, vp, sz, vp]
+        L.nslam_scene_workspace_size.argtypes = [i64, i32, i32, i32]
+        L.nslam_scene_workspace_size.restype = sz
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L
