@@ -542,6 +542,87 @@ int nslam_mesh_select(const int32_t* faces, int64_t n_faces, const int32_t* labe
 /* out[f][c] = new_id[faces[f][c]]. */
 int nslam_mesh_remap(const int32_t* faces, int64_t n_faces, const int32_t* new_id, int32_t* out, void* stream);
 
+/* TSDF fusion of depth frames (the volume of Mesher.get_bound_from_frames, src/utils/Mesher.py:214-279;
+ * csrc/nslam_tsdf.hip); additive, no ABI bump.  The algorithm of open3d's ScalableTSDFVolume /
+ * UniformTSDFVolume, restated; the library is absent, so parity with it is unpinned.
+ *
+ * Geometry: voxel edge L (`voxel`), truncation `trunc` with 2 trunc <= 16 L, blocks of 16^3 voxels with edge
+ * B = 16.0 * L anchored at the world origin: a point p lies in block floor(p / B) per axis (true floor).
+ * Voxel (gx, gy, gz) (global integer index, block * 16 + local) has its centre at ((double)g + 0.5) * L, rounded
+ * to float32 for the projection.
+ * Storage: a dense int32 table over the box of block indices [block_lo, block_hi) per axis (HOST int32 [3]
+ * each; cell key = ((bx - lo.x) * ny + (by - lo.y)) * nz + (bz - lo.z); an entry is a pool id or -1), and a
+ * pool of n_pool blocks: tsdf float32 [n_pool][4096], weight float32 [n_pool][4096], colour float32
+ * [3][color_stride] with channel c of voxel i at color_pool[c * color_stride + i] (color_stride >= 4096 n_pool),
+ * a voxel at (x * 16 + y) * 16 + z of its block.  pool_key int32 [n_pool] is a block's cell key.  The box is not
+ * empty, has at most 2^27 cells and indices within +-2^26.  No kernel allocates: the caller grows the pool
+ * before nslam_tsdf_integrate, and every table and pool index is checked before use.
+ * Poses: c2w float64 [K][16] and w2c float32 [K][16] (row-major, device) are a camera's pose and its inverse
+ * (inverted by the caller on the host) in the +z-forward, y-down convention.
+ * A depth d is valid when d > 0 && d <= depth_trunc (NaN is not).  Samples are the pixels with u % stride == 0
+ * and v % stride == 0.  For a valid sample, in float64 without FMA contraction:
+ *   p_cam = (((u - cx) * d) / fx, ((v - cy) * d) / fy, d);   p = ((m0 x + m1 y) + m2 z) + m3 per row of c2w
+ * and its blocks are floor((p - trunc) / B) .. floor((p + trunc) / B) per axis (1 to 8 blocks; indices saturate
+ * at +-2^30, a p that is not finite makes the sample invalid).
+ *
+ * nslam_tsdf_block_range: bounds int32 [6] = the per-axis minimum of floor((p - trunc) / B) and maximum of
+ * floor((p + trunc) / B) over the valid samples of n_frames >= 1 frames (INT32_MAX / INT32_MIN without one),
+ * n_valid int64 = their number.  Integer atomicMin / atomicMax / atomicAdd.
+ * nslam_tsdf_touch (n_frames <= 32): mask uint32 [cells], zeroed here, gets bit f ORed into every block of
+ * every valid sample of frame f; blocks outside the table are skipped and n_outside int64 counts the samples
+ * that have one.
+ * nslam_tsdf_integrate (n_frames <= 32): list_key / list_id / list_mask [n_list] are the cell key, pool id and
+ * touch mask of the blocks with a non-zero mask.  Every voxel of a listed block loops over the set bits of its
+ * block's mask in ascending frame order (a frame updates only the blocks its own samples touched) with its state
+ * in registers: one read and one write per call.  Per voxel centre p and frame, float32 without FMA contraction:
+ *   cam = ((m0 p.x + m1 p.y) + m2 p.z) + m3 per row of w2c;            skip unless cam.z > 0
+ *   uf = ((cam.x * fx) / cam.z + cx) + 0.5f,  vf likewise;               skip unless 1e-4f <= uf < (float)W - 1e-4f
+ *   u = (int)uf, v = (int)vf;  d = depth[f][v][u];                       (and vf with H); skip an invalid d
+ *   xn = ((float)u - cx) / fx,  yn likewise;  m = sqrtf((xn xn + yn yn) + 1.0f)
+ *   sdf = (d - cam.z) * m;                                               skip unless sdf > -trunc
+ *   t = fminf(1.0f, sdf * (1.0f / trunc))
+ *   tsdf = (tsdf * w + t) / (w + 1.0f);  each colour channel the same way from color uint8 [K][H][W][3] at
+ *   (u, v) (when color_pool is not NULL; color must then be given);  w = w + 1.0f
+ * nslam_tsdf_mc_count / nslam_tsdf_mc_emit: marching cubes with the voxel centres as lattice points.  A cell
+ * is valid when its 8 corners lie in allocated blocks (neighbours through the table) and have weight > 0; a
+ * corner is below when tsdf < 0; every voxel owns its +x, +y, +z edges; an edge has a vertex if and only if its
+ * ends differ and a valid cell contains it.  Count writes flags uint8 [4096 n_pool][3] (zeroed here) and ntri
+ * uint8 [4096 n_pool]; the caller forms the exclusive int32 prefix sums vert_off and face_off, as for
+ * nslam_mc_count.  Emit writes verts float64 [n_verts][3] = (((double)g + 0.5) + t) * L along the edge with
+ * t = f0 / (f0 - f1) in float32, colors uint8 [n_verts][3] = floor(c + 0.5f) clamped, c = (|f1| c0 + |f0| c1) /
+ * (|f0| + |f1|) in float32 (when color_pool and colors are given), and faces int32 [n_faces][3] from the loops
+ * of csrc/nslam_mc_table.h with the winding flipped: right-hand normals point toward increasing TSDF, the free
+ * side.  A row of that table is a fan per loop from the loop's first vertex; here every loop (l0 .. l(n-1)) is
+ * fanned instead from its first vertex lk none of whose diagonals (lk, lj), j not adjacent to k, lies in a face
+ * of the cell (two edges lie in a common face when they share an (axis, side) pair; every loop of every case
+ * has such a vertex): triangles (lk, l(k+i), l(k+i+1)), i = 1 .. n-2, indices mod n, in the row's loop order.
+ * A diagonal then belongs to two triangles of its own cell only, so no mesh edge has more than two faces, also
+ * where a face of a cell holds four crossings.  Vertices are in pool / owner-edge order, faces in pool / cell
+ * order.
+ * NSLAM_EINVAL (before any device call): a null pointer, n_frames outside its range, stride < 1, voxel or trunc
+ * not positive, 2 trunc > 16 voxel, an empty or oversized box.  NSLAM_EUNSUPPORTED: 3 * 4096 * n_pool >= 2^31,
+ * H * W >= 2^31.  No valid sample, n_list == 0, n_pool == 0 and no crossing are legal. */
+int nslam_tsdf_block_range(const float* depth, const double* c2w, int32_t n_frames, int32_t H, int32_t W, double fx,
+                           double fy, double cx, double cy, int32_t stride, float depth_trunc, double voxel,
+                           double trunc, int32_t* bounds, int64_t* n_valid, void* stream);
+int nslam_tsdf_touch(const float* depth, const double* c2w, int32_t n_frames, int32_t H, int32_t W, double fx,
+                     double fy, double cx, double cy, int32_t stride, float depth_trunc, double voxel, double trunc,
+                     const int32_t* block_lo, const int32_t* block_hi, uint32_t* mask, int64_t* n_outside,
+                     void* stream);
+int nslam_tsdf_integrate(const float* depth, const uint8_t* color, const float* w2c, int32_t n_frames, int32_t H,
+                         int32_t W, float fx, float fy, float cx, float cy, float depth_trunc, double voxel,
+                         float trunc, const int32_t* block_lo, const int32_t* block_hi, const int32_t* list_key,
+                         const int32_t* list_id, const uint32_t* list_mask, int64_t n_list, int64_t n_pool,
+                         float* tsdf, float* weight, float* color_pool, int64_t color_stride, void* stream);
+int nslam_tsdf_mc_count(const float* tsdf, const float* weight, const int32_t* pool_key, int64_t n_pool,
+                        const int32_t* table, const int32_t* block_lo, const int32_t* block_hi, uint8_t* flags,
+                        uint8_t* ntri, void* stream);
+int nslam_tsdf_mc_emit(const float* tsdf, const float* weight, const float* color_pool, int64_t color_stride,
+                       const int32_t* pool_key, int64_t n_pool, const int32_t* table, const int32_t* block_lo,
+                       const int32_t* block_hi, double voxel, const uint8_t* flags, const uint8_t* ntri,
+                       const int32_t* vert_off, const int32_t* face_off, int64_t n_verts, int64_t n_faces,
+                       double* verts, uint8_t* colors, int32_t* faces, void* stream);
+
 /* Evaluation (src/tools/cull_mesh.py, src/tools/eval_recon.py; csrc/nslam_eval.hip); additive, no ABI bump.
  * No entry point here uses atomics, with one exception: nslam_raster_depth (and the replay's nslam_scene_render on
  * the same passes) combines its hits with an integer atomicMin, which does not depend on the order.  Every output

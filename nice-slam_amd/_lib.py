@@ -167,6 +167,9 @@ EXPORTS = (
     "nslam_vis_panels",
     # replay: the scene renderer of visualizer.py's frames (additive: no ABI bump)
     "nslam_scene_render", "nslam_scene_workspace_size",
+    # TSDF fusion: block range, touch masks, integration, marching cubes over the pool (additive: no ABI bump)
+    "nslam_tsdf_block_range", "nslam_tsdf_touch", "nslam_tsdf_integrate", "nslam_tsdf_mc_count",
+    "nslam_tsdf_mc_emit",
 )
 
 _lib = None
@@ -296,6 +299,14 @@ def lib():
                                          f64, f64, f64, f64, f64, i32, u8x3, f64, i64, i32, vp, vp, vp, vp, sz, vp]
         L.nslam_scene_workspace_size.argtypes = [i64, i32, i32, i32]
         L.nslam_scene_workspace_size.restype = sz
+        L.nslam_tsdf_block_range.argtypes = [vp, vp, i32, i32, i32, f64, f64, f64, f64, i32, f32, f64, f64, vp, vp, vp]
+        L.nslam_tsdf_touch.argtypes = [vp, vp, i32, i32, i32, f64, f64, f64, f64, i32, f32, f64, f64, i32p, i32p, vp,
+                                       vp, vp]
+        L.nslam_tsdf_integrate.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, f64, f32, i32p, i32p,
+                                           vp, vp, vp, i64, i64, vp, vp, vp, i64, vp]
+        L.nslam_tsdf_mc_count.argtypes = [vp, vp, vp, i64, vp, i32p, i32p, vp, vp, vp]
+        L.nslam_tsdf_mc_emit.argtypes = [vp, vp, vp, i64, vp, i64, vp, i32p, i32p, f64, vp, vp, vp, vp, i64, i64, vp,
+                                         vp, vp, vp]
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L

@@ -8,8 +8,10 @@ written here.  Torch does allocation, cumsum, boolean indexing and batching only
 are not imported.
 
 Deviations from the reference, all stated in DESIGN.md §7a:
-  * get_bound_from_frames back-projects the keyframe depths directly instead of fusing an open3d TSDF first,
-    and returns the hull as half-spaces [M,4] (float64) rather than a trimesh object;
+  * get_bound_from_frames has two methods, chosen by meshing.bound_from: 'points' (the default) back-projects
+    the keyframe depths directly on the host; 'tsdf' fuses them into a TSDF volume on the device first, as the
+    reference does with open3d (tsdf.TSDFVolume, a restatement: parity with open3d itself is unpinned, §7h).
+    Either way the hull comes back as half-spaces [M,4] (float64) rather than a trimesh object;
   * the hull test is a half-space test, trimesh's `contains` a ray test;
   * trimesh's vertex merging on construction (process=True) is not reproduced: the mesh is already indexed;
   * 'render_ray_along_normal' (iMAP*'s colour mode, Mesher.py:526-553) is implemented for nice=False: the vertex
@@ -125,6 +127,7 @@ class Mesher(object):
         self.color_mesh_extraction_method = m["color_mesh_extraction_method"]
         self.get_largest_components = m["get_largest_components"]
         self.depth_test = m["depth_test"]
+        self.bound_from = m.get("bound_from", "points")  # get_bound_from_frames' default method
 
         self.bound = slam.bound
         self.nice = slam.nice
@@ -175,16 +178,40 @@ class Mesher(object):
                                           get_mask_use_all_frames)
         return s.cpu().numpy(), f.cpu().numpy(), u.cpu().numpy()
 
-    def get_bound_from_frames(self, keyframe_dict, scale=1, stride=8):
-        """The convex hull of the keyframes' back-projected depths (every `stride`-th pixel) and camera
-        centres, scaled about its centre by clean_mesh_bound_scale → half-spaces float64 [M,4] (numpy):
-        a point p is inside when planes @ (p, 1) <= 0.  `scale` is accepted for signature parity (the
-        reference sizes its TSDF voxels with it; there is no TSDF here)."""
+    def get_bound_from_frames(self, keyframe_dict, scale=1, stride=8, method=None, device=None):
+        """The convex hull that bounds the mesh, scaled about its centre by clean_mesh_bound_scale → half-spaces
+        float64 [M,4] (numpy): a point p is inside when planes @ (p, 1) <= 0.
+
+        method (default: cfg['meshing']['bound_from'], else 'points'):
+          'points'  the hull of the keyframes' back-projected depths (every `stride`-th pixel, on the host) and
+                    camera centres; `scale` is accepted for signature parity only;
+          'tsdf'    the reference's construction (Mesher.py:214-279): the keyframes fused into a TSDF volume
+                    with voxel 4 scale / 512 and truncation 0.04 scale on `device` (default: the depths' own
+                    device when that is a HIP device, else cuda:0), the hull of the camera centres and the
+                    vertices of the volume's mesh; `stride` is not used (the volume samples every 4th pixel).
+                    The keyframes' poses are read, never edited."""
+        if method is None:
+            method = self.bound_from
+        if method not in ("points", "tsdf"):
+            raise ValueError(f"get_bound_from_frames: unknown method {method!r} (have 'points', 'tsdf')")
         try:
             from scipy.spatial import ConvexHull
         except ImportError as e:
             raise ImportError("Mesher.get_bound_from_frames needs scipy (scipy.spatial.ConvexHull); install "
                               "it, or pass get_mesh(..., mesh_bound=planes)") from e
+        if method == "tsdf":
+            pts = self._tsdf_hull_points(keyframe_dict, scale, device)
+        else:
+            pts = self._depth_hull_points(keyframe_dict, stride)
+        hull = ConvexHull(pts)
+        eq = np.array(hull.equations, dtype=np.float64)  # n . x + d <= 0 inside, |n| = 1
+        centre = pts[hull.vertices].mean(0)
+        s = float(self.clean_mesh_bound_scale)
+        nc = eq[:, :3] @ centre
+        eq[:, 3] = s * (nc + eq[:, 3]) - nc  # x' = centre + s (x - centre)
+        return eq
+
+    def _depth_hull_points(self, keyframe_dict, stride):
         H, W, fx, fy, cx, cy = self.H, self.W, self.fx, self.fy, self.cx, self.cy
         jj, ii = np.meshgrid(np.arange(0, H, stride, dtype=np.float64), np.arange(0, W, stride, dtype=np.float64),
                              indexing="ij")
@@ -196,14 +223,39 @@ class Mesher(object):
             ok = d > 0
             pts.append((dirs[ok] * d[ok, None]) @ c2w[:3, :3].T + c2w[:3, 3])
             pts.append(c2w[None, :3, 3])
-        pts = np.concatenate(pts, 0)
-        hull = ConvexHull(pts)
-        eq = np.array(hull.equations, dtype=np.float64)  # n . x + d <= 0 inside, |n| = 1
-        centre = pts[hull.vertices].mean(0)
-        s = float(self.clean_mesh_bound_scale)
-        nc = eq[:, :3] @ centre
-        eq[:, 3] = s * (nc + eq[:, 3]) - nc  # x' = centre + s (x - centre)
-        return eq
+        return np.concatenate(pts, 0)
+
+    def fuse_keyframes(self, keyframe_dict, scale=1, device=None):
+        """The keyframes' depths (and colours, when every keyframe has one) fused into a tsdf.TSDFVolume with
+        the reference's voxel size 4 scale / 512 and truncation 0.04 scale; None when no depth sample is
+        valid.  Poses are converted to the volume's +z-forward convention on copies."""
+        from .tsdf import TSDFVolume, opengl_to_cv
+        if device is None:
+            d0 = keyframe_dict[0]["depth"].device
+            device = d0 if d0.type == "cuda" else torch.device("cuda:0")
+        H, W, fx, fy, cx, cy = self.H, self.W, self.fx, self.fy, self.cx, self.cy
+        c2w = np.stack([opengl_to_cv(kf["est_c2w"]) for kf in keyframe_dict], 0)
+        depth = torch.stack([kf["depth"].detach().to(device).float().reshape(H, W) for kf in keyframe_dict],
+                            0).contiguous()
+        color = None
+        if all(kf.get("color") is not None for kf in keyframe_dict):
+            color = torch.stack([(kf["color"].detach().to(device).float().reshape(H, W, 3) * 255).to(torch.uint8)
+                                 for kf in keyframe_dict], 0).contiguous()
+        voxel, trunc = 4.0 * scale / 512.0, 0.04 * scale
+        lo, hi, n_valid = TSDFVolume.block_range(depth, c2w, H, W, fx, fy, cx, cy, voxel, trunc)
+        if n_valid == 0:
+            return None
+        vol = TSDFVolume(voxel, trunc, lo, hi, device, color=color is not None)
+        vol.integrate(depth, color, c2w, fx, fy, cx, cy)
+        return vol
+
+    def _tsdf_hull_points(self, keyframe_dict, scale, device):
+        centres = np.stack([kf["est_c2w"].detach().cpu().numpy().astype(np.float64)[:3, 3]
+                            for kf in keyframe_dict], 0)
+        vol = self.fuse_keyframes(keyframe_dict, scale, device)
+        if vol is None:
+            return centres
+        return np.concatenate([centres, vol.extract_mesh()["vertices"].cpu().numpy()], 0)
 
     def eval_points(self, p, decoders, c=None, stage="color", device="cuda:0"):
         """Mesher.eval_points (Mesher.py:281-319): raw [N,4] in batches; points outside the bound get logit 100."""
@@ -256,7 +308,7 @@ class Mesher(object):
     # -------------------------------------------------------------------------------------------
     def _planes(self, mesh_bound, keyframe_dict, device):
         if mesh_bound is None:
-            mesh_bound = self.get_bound_from_frames(keyframe_dict, self.scale)
+            mesh_bound = self.get_bound_from_frames(keyframe_dict, self.scale, device=device)
         if not isinstance(mesh_bound, torch.Tensor):
             mesh_bound = torch.from_numpy(np.asarray(mesh_bound, dtype=np.float64))
         return mesh_bound.to(device=device, dtype=torch.float64).contiguous()

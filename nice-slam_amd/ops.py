@@ -1740,3 +1740,130 @@ def sample_importance(z, weights, n_importance, merged=True):
                                                stream_ptr(z.device))
         check(rc, "nslam_sample_importance")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# TSDF fusion (csrc/nslam_tsdf.hip); the volume itself is tsdf.TSDFVolume
+# ------------------------------------------------------------------------------------------------
+def _i3(v, name):
+    if len(v) != 3:
+        raise ValueError(f"{name}: three block indices expected")
+    return (ctypes.c_int32 * 3)(*[int(x) for x in v])
+
+
+def _tsdf_frames(depth, c2w, H, W):
+    _want(depth, "depth", torch.float32, (None, int(H), int(W)))
+    k = int(depth.shape[0])
+    _want(c2w, "c2w", torch.float64, (k, 4, 4))
+    return k
+
+
+def tsdf_block_range(depth, c2w, H, W, fx, fy, cx, cy, stride, depth_trunc, voxel, trunc):
+    """nslam_tsdf_block_range → (bounds int32 [6]: min x, y, z, max x, y, z; n_valid int64 [1]), on the device.
+
+    depth float32 [K,H,W]; c2w float64 [K,4,4] (+z forward)."""
+    k = _tsdf_frames(depth, c2w, H, W)
+    dev = depth.device
+    bounds = torch.empty(6, dtype=torch.int32, device=dev)
+    n_valid = torch.empty(1, dtype=torch.int64, device=dev)
+    rc = lib().nslam_tsdf_block_range(ptr(depth), ptr(c2w), k, int(H), int(W), float(fx), float(fy), float(cx),
+                                      float(cy), int(stride), float(depth_trunc), float(voxel), float(trunc),
+                                      ptr(bounds), ptr(n_valid), stream_ptr(dev))
+    check(rc, "nslam_tsdf_block_range")
+    return bounds, n_valid
+
+
+def tsdf_touch(depth, c2w, H, W, fx, fy, cx, cy, stride, depth_trunc, voxel, trunc, block_lo, block_hi):
+    """nslam_tsdf_touch → (mask int32 [cells]: bit f = frame f's samples reach the block, in table order;
+    n_outside int64 [1]), on the device.  At most 32 frames."""
+    k = _tsdf_frames(depth, c2w, H, W)
+    dev = depth.device
+    lo, hi = _i3(block_lo, "block_lo"), _i3(block_hi, "block_hi")
+    cells = max(0, hi[0] - lo[0]) * max(0, hi[1] - lo[1]) * max(0, hi[2] - lo[2])
+    if not 0 < cells <= 1 << 27:
+        raise ValueError(f"tsdf_touch: the block table [{list(lo)}, {list(hi)}) must hold 1 to 2^27 cells")
+    mask = torch.empty(cells, dtype=torch.int32, device=dev)
+    n_out = torch.empty(1, dtype=torch.int64, device=dev)
+    rc = lib().nslam_tsdf_touch(ptr(depth), ptr(c2w), k, int(H), int(W), float(fx), float(fy), float(cx), float(cy),
+                                int(stride), float(depth_trunc), float(voxel), float(trunc), lo, hi, ptr(mask),
+                                ptr(n_out), stream_ptr(dev))
+    check(rc, "nslam_tsdf_touch")
+    return mask, n_out
+
+
+def tsdf_integrate(depth, color, w2c, H, W, fx, fy, cx, cy, depth_trunc, voxel, trunc, block_lo, block_hi, list_key,
+                   list_id, list_mask, n_pool, tsdf, weight, color_pool):
+    """nslam_tsdf_integrate, in place on tsdf / weight [cap,4096] and color_pool [3,cap,4096] (or None).
+
+    depth float32 [K,H,W]; color uint8 [K,H,W,3] or None; w2c float32 [K,4,4]; list_* int32 [n_list]."""
+    _want(depth, "depth", torch.float32, (None, int(H), int(W)))
+    k = int(depth.shape[0])
+    _want(w2c, "w2c", torch.float32, (k, 4, 4))
+    n_list = int(list_key.shape[0])
+    for name, t in (("list_key", list_key), ("list_id", list_id), ("list_mask", list_mask)):
+        _want(t, name, torch.int32, (n_list,))
+    cap = int(tsdf.shape[0])
+    if not 0 <= int(n_pool) <= cap:
+        raise ValueError("tsdf_integrate: n_pool exceeds the pool's capacity")
+    _want(tsdf, "tsdf", torch.float32, (cap, 4096))
+    _want(weight, "weight", torch.float32, (cap, 4096))
+    if color_pool is not None:
+        _want(color_pool, "color_pool", torch.float32, (3, cap, 4096))
+        if color is None:
+            raise ValueError("tsdf_integrate: a volume with colour needs colour images")
+        _want(color, "color", torch.uint8, (k, int(H), int(W), 3))
+    else:
+        color = None
+    dev = depth.device
+    rc = lib().nslam_tsdf_integrate(ptr(depth), ptr(color), ptr(w2c), k, int(H), int(W), float(fx), float(fy),
+                                    float(cx), float(cy), float(depth_trunc), float(voxel), float(trunc),
+                                    _i3(block_lo, "block_lo"), _i3(block_hi, "block_hi"), ptr(list_key),
+                                    ptr(list_id), ptr(list_mask), n_list, int(n_pool), ptr(tsdf), ptr(weight),
+                                    ptr(color_pool), cap * 4096, stream_ptr(dev))
+    check(rc, "nslam_tsdf_integrate")
+
+
+def tsdf_marching_cubes(tsdf, weight, color_pool, pool_key, n_pool, table, block_lo, block_hi, voxel):
+    """nslam_tsdf_mc_count / nslam_tsdf_mc_emit over the first n_pool blocks → (verts float64 [V,3], faces int32
+    [F,3], colors uint8 [V,3] or None), vertices in pool / owner-edge order, faces in pool / cell order."""
+    cap, n_pool = int(tsdf.shape[0]), int(n_pool)
+    if not 0 <= n_pool <= cap:
+        raise ValueError("tsdf_marching_cubes: n_pool exceeds the pool's capacity")
+    _want(tsdf, "tsdf", torch.float32, (cap, 4096))
+    _want(weight, "weight", torch.float32, (cap, 4096))
+    if color_pool is not None:
+        _want(color_pool, "color_pool", torch.float32, (3, cap, 4096))
+    _want(pool_key, "pool_key", torch.int32, (None,))
+    if int(pool_key.shape[0]) < n_pool:
+        raise ValueError("tsdf_marching_cubes: pool_key is shorter than the pool")
+    lo, hi = _i3(block_lo, "block_lo"), _i3(block_hi, "block_hi")
+    cells = max(0, hi[0] - lo[0]) * max(0, hi[1] - lo[1]) * max(0, hi[2] - lo[2])
+    _want(table, "table", torch.int32, (cells,))
+    dev = tsdf.device
+    n = n_pool * 4096
+    verts = torch.empty(0, 3, dtype=torch.float64, device=dev)
+    faces = torch.empty(0, 3, dtype=torch.int32, device=dev)
+    colors = None if color_pool is None else torch.empty(0, 3, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return verts, faces, colors
+    flags = torch.empty(3 * n, dtype=torch.uint8, device=dev)
+    ntri = torch.empty(n, dtype=torch.uint8, device=dev)
+    rc = lib().nslam_tsdf_mc_count(ptr(tsdf), ptr(weight), ptr(pool_key), n_pool, ptr(table), lo, hi, ptr(flags),
+                                   ptr(ntri), stream_ptr(dev))
+    check(rc, "nslam_tsdf_mc_count")
+    vinc = torch.cumsum(flags, 0, dtype=torch.int32)
+    finc = torch.cumsum(ntri, 0, dtype=torch.int32)
+    n_verts, n_faces = int(vinc[-1]), int(finc[-1])
+    if n_verts == 0 and n_faces == 0:
+        return verts, faces, colors
+    verts = torch.empty(n_verts, 3, dtype=torch.float64, device=dev)
+    faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
+    if color_pool is not None:
+        colors = torch.empty(n_verts, 3, dtype=torch.uint8, device=dev)
+    voff = (vinc - flags).contiguous()
+    foff = (finc - ntri).contiguous()
+    rc = lib().nslam_tsdf_mc_emit(ptr(tsdf), ptr(weight), ptr(color_pool), cap * 4096, ptr(pool_key), n_pool,
+                                  ptr(table), lo, hi, float(voxel), ptr(flags), ptr(ntri), ptr(voff), ptr(foff),
+                                  n_verts, n_faces, ptr(verts), ptr(colors), ptr(faces), stream_ptr(dev))
+    check(rc, "nslam_tsdf_mc_emit")
+    return verts, faces, colors
