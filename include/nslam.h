@@ -42,10 +42,10 @@ enum {
 
 enum { NSLAM_STAGE_COARSE = 0, NSLAM_STAGE_MIDDLE = 1, NSLAM_STAGE_FINE = 2, NSLAM_STAGE_COLOR = 3 };
 enum { NSLAM_DEC_COARSE = 0, NSLAM_DEC_MIDDLE = 1, NSLAM_DEC_FINE = 2, NSLAM_DEC_COLOR = 3 };
-/* nslam_query_cfg.fwd_variant (ABI v18): UNITS = one one-wave workgroup per decoder and 32-point tile;
- * PC = one persistent workgroup per CU whose producer waves gather and embed while its consumer waves
- * run the decoder GEMM chains; PARTS = 4-wave workgroups of one decoder part. */
-enum { NSLAM_FWD_DEFAULT = 0, NSLAM_FWD_UNITS = 1, NSLAM_FWD_PC = 2, NSLAM_FWD_PARTS = 3 };
+/* nslam_query_cfg.fwd_variant (ABI v18): nslam_query_fwd_ws has one kernel, UNITS = one one-wave
+ * workgroup per decoder and 32-point tile, and DEFAULT means it.  The values 2 and 3 named forwards
+ * that were retired; they, and every other value, are NSLAM_EINVAL. */
+enum { NSLAM_FWD_DEFAULT = 0, NSLAM_FWD_UNITS = 1 };
 
 /* One feature grid (src/NICE_SLAM.py:192-250) with the bound it is normalised against
  * (decoder.bound, src/NICE_SLAM.py:152-157; the coarse decoder uses bound*2). */

@@ -62,7 +62,7 @@ class NslamQueryCfg(ctypes.Structure):
         ("n_samples", ctypes.c_int64),
         ("saved_masks", ctypes.c_void_p),
         ("defer_occ", ctypes.c_int32),  # ABI v7
-        ("fwd_variant", ctypes.c_int32),  # ABI v18 (NSLAM_FWD_*)
+        ("fwd_variant", ctypes.c_int32),  # ABI v18 (NSLAM_FWD_*: 0 default = 1 units, the one kernel)
         ("act_tape", ctypes.c_void_p),  # ABI v9: colour-decoder activation tape (NULL = none)
         ("g_h4", ctypes.c_void_p),  # ABI v17: colour decoder's d/dh4 [M][32] (NULL = none)
     ]

@@ -33,14 +33,7 @@ extern "C" size_t nslam_query_fwd_workspace_size(const nslam_query_cfg* cfg, int
   return (((size_t)n_pts * sizeof(float) + 255) & ~(size_t)255) + 256;  // the middle occupancy + 256 reserved
 }
 
-namespace {
-typedef void (*FwdKernel)(QueryKArgs, float*);
-template <int STAGE, bool TAPE>
-constexpr FwdKernel k_parts2 = k_query_fwd_parts<STAGE, 2, TAPE>;
-template <int STAGE, bool TAPE>
-constexpr FwdKernel k_parts3 = k_query_fwd_parts<STAGE, 3, TAPE>;
-}  // namespace
-// The <STAGE, TAPE> instantiation of a decoder-parallel forward kernel K for cfg: the fine stage, or the
+// The <STAGE, TAPE> instantiation of the decoder-parallel forward kernel K for cfg: the fine stage, or the
 // colour stage with / without the activation tape (local to nslam_query_fwd_ws)
 #define COLOR_KERNEL(K) (cfg->act_tape ? K<NSLAM_STAGE_COLOR, true> : K<NSLAM_STAGE_COLOR, false>)
 #define STAGE_KERNEL(K) (cfg->stage == NSLAM_STAGE_FINE ? K<NSLAM_STAGE_FINE, false> : COLOR_KERNEL(K))
@@ -51,45 +44,22 @@ extern "C" int nslam_query_fwd_ws(const nslam_query_cfg* cfg, const double* pts,
   if (need == 0) return nslam_query_fwd(cfg, pts, n_pts, raw, stream);  // coarse / middle: one decoder
   const int rc = check_cfg(cfg, false);
   if (rc) return rc;
+  // One kernel serves this entry point (one-wave workgroups per decoder and tile), so cfg->fwd_variant
+  // and NSLAM_FWD_MODE only name it: default / units.  A retired or misspelt value is an error, not a
+  // silent fallback: it must not run a kernel other than the one asked for.
+  static const bool env_ok = [] {
+    const char* e = getenv("NSLAM_FWD_MODE");
+    return !e || !*e || !strcmp(e, "units");
+  }();
+  if (cfg->fwd_variant != NSLAM_FWD_DEFAULT && cfg->fwd_variant != NSLAM_FWD_UNITS) return NSLAM_EINVAL;
+  if (!env_ok) return NSLAM_EINVAL;
   if (!ws || ws_bytes < need) return NSLAM_EWORKSPACE;
   if (check_points(cfg, pts, n_pts, raw != nullptr) || (((uintptr_t)raw) & 15)) return NSLAM_EINVAL;
-  // forward variant: cfg->fwd_variant, else NSLAM_FWD_MODE=units (one-wave workgroups per decoder-tile;
-  // the default), pc (producer / consumer waves, one persistent workgroup per CU) or parts
-  // (an unrecognised NSLAM_FWD_MODE is an error, not a silent fallback: a typo must not change the kernel)
-  static const int env_variant = [] {
-    const char* e = getenv("NSLAM_FWD_MODE");
-    if (!e || !*e || !strcmp(e, "units")) return (int)NSLAM_FWD_UNITS;
-    return !strcmp(e, "pc") ? (int)NSLAM_FWD_PC : !strcmp(e, "parts") ? (int)NSLAM_FWD_PARTS : -1;
-  }();
-  if (cfg->fwd_variant < 0 || cfg->fwd_variant > NSLAM_FWD_PARTS) return NSLAM_EINVAL;
-  const int variant = cfg->fwd_variant == NSLAM_FWD_DEFAULT ? env_variant : cfg->fwd_variant;
-  if (variant < 0) return NSLAM_EINVAL;
-  static const int64_t n_cus = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    return (int64_t)cus;
-  }();
   QueryKArgs a{*cfg, pts, n_pts, raw, nullptr, nullptr};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   float* occ = reinterpret_cast<float*>(ws);  // the middle occupancy [n_pts] (the 256 bytes after it: reserved)
-  const int64_t tiles = (n_pts + 31) / 32, groups = (tiles + 3) / 4;
-  const int64_t units = tiles * (cfg->stage == NSLAM_STAGE_COLOR ? 3 : 2);
-  if (variant == NSLAM_FWD_PC) {
-    hipLaunchKernelGGL(STAGE_KERNEL(k_query_fwd_pc), dim3((unsigned)(units < n_cus ? units : n_cus)),
-                       dim3(64 * kPcWaves), 0, s, a, occ);
-  } else if (variant == NSLAM_FWD_UNITS) {
-    hipLaunchKernelGGL(STAGE_KERNEL(k_query_fwd_units), dim3((unsigned)units), dim3(64), 0, s, a, occ);
-  } else if (cfg->stage == NSLAM_STAGE_COLOR && 3 * tiles <= n_cus * 4 * 3) {
-    // Colour stage: 3 parts (middle | fine | colour) while 3 waves per tile fit the chip's wave slots
-    // in one round (3 per SIMD at the forward's 168 VGPRs; e.g. tracking, 300 tiles), else 2 parts
-    // (middle then colour | fine: fewer, balanced waves — room0 mapping: 3000 instead of 4500 for
-    // 4096 slots, 187 -> 198 M ray-samples/s)
-    hipLaunchKernelGGL(COLOR_KERNEL(k_parts3), dim3((unsigned)(groups * 3)), dim3(256), 0, s, a, occ);
-  } else {
-    hipLaunchKernelGGL(STAGE_KERNEL(k_parts2), dim3((unsigned)(groups * 2)), dim3(256), 0, s, a, occ);
-  }
+  const int64_t units = (n_pts + 31) / 32 * (cfg->stage == NSLAM_STAGE_COLOR ? 3 : 2);
+  hipLaunchKernelGGL(STAGE_KERNEL(k_query_fwd_units), dim3((unsigned)units), dim3(64), 0, s, a, occ);
   if (!cfg->defer_occ)  // else the consumer adds ws on read (nslam_loss_cfg.occ_add)
     hipLaunchKernelGGL(k_occ_combine, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, s, raw, occ, n_pts);
   return hip_status();

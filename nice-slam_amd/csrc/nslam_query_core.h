@@ -149,23 +149,7 @@ __device__ __forceinline__ void tl_mark(int slot, int end, long long tag) {
   }
 }
 #define TL(slot, end, tag) tl_mark(slot, end, tag)
-// add v << 8 into this wave's tag (after its start mark): e.g. the 10-ns ticks a wave spent waiting
-// (field f = 0: bits 8-31, f = 1: bits 32-55 — e.g. a producer's gather time)
-__device__ __forceinline__ void tl_add(int slot, unsigned long long v, int f = 0) {
-  const int64_t w_ = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if ((threadIdx.x & 63) == 0 && w_ < kTlWaves) g_tl[((size_t)slot * kTlWaves + w_) * 4 + 3] += v << (8 + 24 * f);
-}
-#define TL_ADD(slot, v) tl_add(slot, v)
-#define TL_ADD1(slot, v) tl_add(slot, v, 1)
-#define TL_NOW() __builtin_amdgcn_s_memrealtime()
 #else
-#define TL_ADD(slot, v) \
-  do {                  \
-  } while (0)
-#define TL_ADD1(slot, v) \
-  do {                   \
-  } while (0)
-#define TL_NOW() 0ull
 #define TL(slot, end, tag) \
   do {                     \
   } while (0)

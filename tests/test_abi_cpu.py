@@ -444,20 +444,43 @@ vp, i64, sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_size_t
 L.nslam_query_fwd_workspace_size.argtypes, L.nslam_query_fwd_workspace_size.restype = [vp, i64], sz
 L.nslam_query_fwd_ws.argtypes = [vp, vp, i64, vp, vp, sz, vp]
 need = L.nslam_query_fwd_workspace_size(cfg, 64)
-print(need, L.nslam_query_fwd_ws(cfg, 4096, 64, 4096, 4096, need, None))
+print(need, L.nslam_query_fwd_ws(cfg, 4096, 64, 4096, 4096, need - int(sys.argv[3]), None))
 """
 
 
 def test_fwd_mode_rejects_retired_and_unknown_values(pkg):
-    """NSLAM_FWD_MODE accepts units, pc and parts: the retired dyn and a misspelt value are NSLAM_EINVAL
-    before any launch (the variable is read once per process, hence the child processes), and the forward
-    workspace keeps its size (the retired variant's 256 reserved bytes included)."""
+    """NSLAM_FWD_MODE accepts units (or unset, or empty): the retired dyn, pc and parts and a misspelt value
+    are NSLAM_EINVAL before any launch (the variable is read once per process, hence the child processes),
+    and the forward workspace keeps its size (the retired variants' 256 reserved bytes included).  The mode
+    is checked before the workspace, so an accepted mode shows without a launch: a call one byte short of
+    workspace returns NSLAM_EWORKSPACE where a rejected mode returns NSLAM_EINVAL."""
     import sys
     cfg = _colour_cfg(pkg)
     assert pkg._lib.lib().nslam_query_fwd_workspace_size(ctypes.byref(cfg), 64) == 256 + 256
     argv = [sys.executable, "-c", _FWD_MODE_CHILD, pkg._lib.LIB_PATH, bytes(cfg).hex()]
-    kids = [subprocess.Popen(argv, env=dict(os.environ, NSLAM_FWD_MODE=mode), stdout=subprocess.PIPE, text=True)
-            for mode in ("dyn", "unit")]
-    for kid in kids:
+    unset = {k: v for k, v in os.environ.items() if k != "NSLAM_FWD_MODE"}
+    # (environment, bytes short of workspace, return code)
+    cases = [(dict(unset, NSLAM_FWD_MODE=mode), 0, "-1") for mode in ("dyn", "unit", "pc", "parts")]
+    cases += [(dict(unset, NSLAM_FWD_MODE="pc"), 1, "-1"), (dict(unset, NSLAM_FWD_MODE="units"), 1, "-3"),
+              (dict(unset, NSLAM_FWD_MODE=""), 1, "-3"), (unset, 1, "-3")]
+    kids = [subprocess.Popen(argv + [str(short)], env=env, stdout=subprocess.PIPE, text=True)
+            for env, short, _ in cases]
+    for kid, (env, short, rc) in zip(kids, cases):
         out = kid.communicate()[0].split()
-        assert kid.returncode == 0 and out == ["512", "-1"], out
+        assert kid.returncode == 0 and out == ["512", rc], (env.get("NSLAM_FWD_MODE"), short, out)
+
+
+def test_fwd_variant_rejects_retired_and_unknown_values(pkg):
+    """nslam_query_cfg.fwd_variant: 0 (default) and 1 (units) name the one kernel; the retired 2 (pc) and 3
+    (parts) and any other value are NSLAM_EINVAL before any launch, with every other argument valid.  An
+    accepted value, one byte short of workspace, is NSLAM_EWORKSPACE (no launch either)."""
+    L = pkg._lib.lib()
+    cfg = _colour_cfg(pkg)
+    need = L.nslam_query_fwd_workspace_size(ctypes.byref(cfg), 64)
+    for v in (2, 3, -1):
+        cfg.fwd_variant = v
+        assert L.nslam_query_fwd_workspace_size(ctypes.byref(cfg), 64) == need
+        assert L.nslam_query_fwd_ws(ctypes.byref(cfg), 4096, 64, 4096, 4096, need, None) == -1, v
+    for v in (0, 1):
+        cfg.fwd_variant = v
+        assert L.nslam_query_fwd_ws(ctypes.byref(cfg), 4096, 64, 4096, 4096, need - 1, None) == -3, v

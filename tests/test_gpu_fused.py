@@ -495,12 +495,12 @@ def test_sparse_exchange_single_rank_is_identity(tiny):
 
 @pytest.mark.parametrize("stage", ["fine", "color"])
 @pytest.mark.parametrize("n_per", [13, 1400])
-def test_forward_variants_bitexact(tiny, stage, n_per):
-    """Every nslam_query_fwd_ws variant (ABI v18 fwd_variant: one-wave units, the persistent producer /
-    consumer workgroups, 4-wave parts) forms the same values in the same order: raw, the saved ReLU
-    masks and the colour decoder's activation tape are bit-identical.  3 x 1400 rays x 48 samples =
-    6300 tiles, ~74 decoder units per CU: the producer / consumer ring wraps ~10 times; 3 x 13 rays: a
-    partial last tile and fewer units than CUs."""
+def test_units_forward_matches_fused_rays_bitexact(tiny, stage, n_per):
+    """The two forwards, ray form: nslam_query_fwd_ws (one wave per decoder and tile, LDS vector section,
+    pipelined weight fragments) and nslam_query_fwd (one wave runs a tile's whole stage) form the same
+    values in the same order: raw, the saved ReLU masks and the colour decoder's activation tape are
+    bit-identical.  3 x 1400 rays x 48 samples = 6300 tiles; 3 x 13 rays: a partial last tile and fewer
+    units than CUs."""
     sc, frames = _frames(tiny)
     nice, c = _nice(sc)
     eng = P.engine.MappingEngine(nice, c, sc.bound, 32, 16, device=DEV)
@@ -510,24 +510,23 @@ def test_forward_variants_bitexact(tiny, stage, n_per):
                                              sc.cy)
     z = P.ops.sample_z(ro, rd, gd, sc.bound, 32, 16)
     outs = {}
-    for v in (P.ops.FWD_UNITS, P.ops.FWD_PC, P.ops.FWD_PARTS):
-        P.ops.FWD_VARIANT = v
-        try:
+    try:
+        for split in (True, False):
+            P.ops.SPLIT_FWD = split
             raw = eng.query_fwd(stage, ro, rd, z, tape=True)
             torch.cuda.synchronize()
-            outs[v] = (raw.clone(), eng._saved.clone(), None if eng._tape is None else eng._tape.clone())
-        finally:
-            P.ops.FWD_VARIANT = P.ops.FWD_DEFAULT
-    ref = outs[P.ops.FWD_UNITS]
-    assert bool(torch.isfinite(ref[0]).all())
+            outs[split] = (raw.clone(), eng._saved.clone(), None if eng._tape is None else eng._tape.clone())
+    finally:
+        P.ops.SPLIT_FWD = True
+    units, fused = outs[True], outs[False]
+    assert bool(torch.isfinite(units[0]).all())
+    assert torch.equal(fused[0], units[0])
     ntiles = (z.numel() + 31) // 32
     decs = [1, 2, 3] if stage == "color" else [1, 2]  # the masks the stage writes: [decoder][tile][5][64]
-    for v, o in outs.items():
-        assert torch.equal(o[0], ref[0]), v
-        m, mr = (x.view(torch.int16).view(4, ntiles, 5, 64)[decs] for x in (o[1], ref[1]))
-        assert torch.equal(m, mr), v
-        if stage == "color":
-            assert torch.equal(o[2], ref[2]), v
+    m, mr = (x.view(torch.int16).view(4, ntiles, 5, 64)[decs] for x in (fused[1], units[1]))
+    assert torch.equal(m, mr)
+    if stage == "color":
+        assert torch.equal(fused[2], units[2])
 
 
 @pytest.mark.parametrize("stage", ["middle", "fine", "color"])

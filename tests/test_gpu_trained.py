@@ -221,8 +221,9 @@ def test_prefix_gradients_match_float64(fx, scene, stage, n):
 # ------------------------------------------------------------------------------------------------------------
 # c. forward variants
 # ------------------------------------------------------------------------------------------------------------
-def fwd_ws(nice, grids, stage, pts, bound, variant, defer):
-    """nslam_query_fwd_ws in pts form → (raw, deferred middle occupancy or None, saved masks, tape or None)."""
+def fwd_ws(nice, grids, stage, pts, bound, split, defer):
+    """nslam_query_fwd_ws (split) or nslam_query_fwd in pts form → (raw, deferred middle occupancy or None,
+    saved masks, tape or None)."""
     ops, lib = P.ops, P._lib.lib()
     decs = ops._DEC_FOR_STAGE[stage]
     packers = {d: nice.decoder(d).packer() for d in decs}
@@ -238,22 +239,20 @@ def fwd_ws(nice, grids, stage, pts, bound, variant, defer):
         tape = torch.zeros(lib.nslam_query_tape_size(n) // 4, dtype=torch.float32, device=DEV)
         cfg.act_tape = tape.data_ptr()
     raw = torch.empty(n, 4, dtype=torch.float32, device=DEV)
-    ops.FWD_VARIANT = variant
-    try:
-        occ = ops.query_fwd_launch(cfg, pts, n, raw, split=True, defer_occ=defer)
-        torch.cuda.synchronize()
-    finally:
-        ops.FWD_VARIANT = ops.FWD_DEFAULT
+    occ = ops.query_fwd_launch(cfg, pts, n, raw, split=split, defer_occ=defer)
+    torch.cuda.synchronize()
     assert (occ is not None) == defer
     return raw, None if occ is None else occ.clone(), saved, tape
 
 
 @pytest.mark.parametrize("stage", ["fine", "color"])
 def test_forward_variants(fx, scene, stage):
+    """The decoder-parallel forward against the fixtures, then itself with the occupancy combine deferred
+    and the fused forward (one wave runs every decoder) against it: raw, masks and tape bit for bit."""
     nice, grids = make_nice(scene), dev_grids(scene, grad=False)
     pts = scene.pts.to(DEV).contiguous()
     case = "eval." + stage
-    base = fwd_ws(nice, grids, stage, pts, scene.bound, P.ops.FWD_UNITS, False)
+    base = fwd_ws(nice, grids, stage, pts, scene.bound, True, False)
     fails = []
     forward_errors(case + ".raw[UNITS]", base[0], fx[case + ".raw"], fx[case + ".floor.raw"],
                    fx[case + ".floor_max.raw"], fails)
@@ -262,18 +261,17 @@ def test_forward_variants(fx, scene, stage):
     decs = [P.ops._DEC_ID[d] for d in P.ops._DEC_FOR_STAGE[stage]]
     masks = lambda s: s.view(torch.int16).view(4, nt, 5, 64)[decs]  # noqa: E731  [decoder][tile][layer][lane]
     assert int((masks(base[2]) != 0).sum()) > 0
-    for variant in (P.ops.FWD_UNITS, P.ops.FWD_PC, P.ops.FWD_PARTS):
-        for defer in (False, True):
-            raw, occ, saved, tape = fwd_ws(nice, grids, stage, pts, scene.bound, variant, defer)
-            tag = f"variant {variant} defer_occ {defer}"
-            full = raw if not defer else torch.cat([raw[:, :3], (raw[:, 3] + occ)[:, None]], 1)
-            bad = torch.nonzero((full != base[0]).any(1)).reshape(-1)
-            assert bad.numel() == 0, f"{tag}: raw differs at {where(int(bad[0]))}"
-            bad = torch.nonzero((masks(saved) != masks(base[2])).reshape(len(decs), nt, -1).any(2).any(0)).reshape(-1)
-            assert bad.numel() == 0, f"{tag}: saved masks differ in tile {int(bad[0])}"
-            if stage == "color":
-                bad = torch.nonzero((tape != base[3]).view(nt, -1).any(1)).reshape(-1)
-                assert bad.numel() == 0, f"{tag}: tape differs in tile {int(bad[0])}"
+    for split, defer in ((True, False), (True, True), (False, False)):
+        raw, occ, saved, tape = fwd_ws(nice, grids, stage, pts, scene.bound, split, defer)
+        tag = f"{'units' if split else 'fused'} defer_occ {defer}"
+        full = raw if not defer else torch.cat([raw[:, :3], (raw[:, 3] + occ)[:, None]], 1)
+        bad = torch.nonzero((full != base[0]).any(1)).reshape(-1)
+        assert bad.numel() == 0, f"{tag}: raw differs at {where(int(bad[0]))}"
+        bad = torch.nonzero((masks(saved) != masks(base[2])).reshape(len(decs), nt, -1).any(2).any(0)).reshape(-1)
+        assert bad.numel() == 0, f"{tag}: saved masks differ in tile {int(bad[0])}"
+        if stage == "color":
+            bad = torch.nonzero((tape != base[3]).view(nt, -1).any(1)).reshape(-1)
+            assert bad.numel() == 0, f"{tag}: tape differs in tile {int(bad[0])}"
 
 
 # ------------------------------------------------------------------------------------------------------------

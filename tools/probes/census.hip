@@ -1,8 +1,9 @@
 // Residency census: how many waves of a kernel with a given VGPR / SGPR / LDS footprint the hardware
 // keeps resident per SIMD at once.  Each wave spins ~20 us (s_memrealtime) and records its start, end
-// and HW_ID | XCC_ID; the host counts the maximum overlap per SIMD.  The forward k_query_fwd_parts
-// (168 VGPRs, 106 SGPRs, 5952 B LDS, 256-thread blocks) was measured at 2 waves per SIMD where the
-// VGPR table says 3 (tools/probes/wave_timeline.py); this separates the candidate causes.
+// and HW_ID | XCC_ID; the host counts the maximum overlap per SIMD.  The round-4 forward (4-wave part
+// workgroups: 168 VGPRs, 106 SGPRs, 5952 B LDS, 256-thread blocks; since replaced by the one-wave
+// k_query_fwd_units) was measured at 2 waves per SIMD where the VGPR table says 3
+// (tools/probes/wave_timeline.py, profiles/r05_census.txt); this separates the candidate causes.
 //   hipcc --offload-arch=gfx950 -O3 tools/probes/census.hip -o tools/probes/census
 #include <hip/hip_runtime.h>
 

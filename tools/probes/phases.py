@@ -41,8 +41,11 @@ def main():
                  9: "out+store", 10: "c.corners", 11: "c.gather", 12: "c.emb+L0+L3e", 13: "c.L1+L2", 14: "c.L3",
                  15: "c.L4"}
     print("nonzero marks per slot:", [int((buf[k] != 0).sum()) for k in range(5)])
-    # room0 colour stage: the 2-part forward (middle then colour | fine), parts alternating along
-    # blockIdx (k_query_fwd_parts); 4 waves per workgroup
+    # room0 colour stage, slot 0 read as 4-wave workgroups alternating (middle then colour | fine) along
+    # blockIdx with marks 0, 1 and 9 around the decoders: the layout of the 4-wave part forward, which is
+    # no longer in the library.  k_query_fwd_units has one wave per workgroup ([0, T) fine, [T, 2T) middle,
+    # [2T, 3T) colour) and writes the per-decoder marks 2-8 and 10-15 only: port this block before
+    # reading a forward breakdown off it.
     groups = (tiles + 3) // 4
     nw = groups * 2 * 4
     t = buf[0, :nw]

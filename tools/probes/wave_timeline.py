@@ -1,7 +1,7 @@
 """Per-wave timeline of the mapping iteration's big kernels (timeline build: make -C nice-slam_amd/csrc timeline).
 
 NSLAM_LIB=nice-slam_amd/libnslam_tl.so python tools/probes/wave_timeline.py [--no-prefetch] [--serial]
-Every wave of k_query_fwd_parts (slot 0), k_dec_bwd_multi (slot 1) and k_color_wgrad (slot 2) records
+Every wave of k_query_fwd_units (slot 0), k_dec_bwd_multi (slot 1) and k_color_wgrad (slot 2) records
 s_memrealtime (100 MHz, one clock for every XCD) at its start and end, and its HW_ID / XCC_ID.  Prints,
 per kernel of the last iteration: the span, when waves start (dispatch), their lifetimes, the waves each
 SIMD received and how many were resident at once, and the mean resident waves per SIMD over the span.
@@ -41,19 +41,13 @@ def analyse(name, t, parts=None):
     print("   start (us after the first)  " + " ".join(f"p{p}={np.percentile((st - t0) * TICK_US, p):.1f}" for p in q))
     print("   end                         " + " ".join(f"p{p}={np.percentile((en - t0) * TICK_US, p):.1f}" for p in q))
     print("   lifetime                    " + " ".join(f"p{p}={np.percentile(life, p):.1f}" for p in q))
-    if parts is not None:
-        waits = ((parts[ok] >> 8) & 0xffffff) * TICK_US  # time the wave spent polling flags (k_query_fwd_pc)
-        field1 = ((parts[ok] >> 32) & 0xffffff) * TICK_US  # a second timed phase (the pc producer's gathers)
+    if parts is not None:  # the wave's tag (the forward: 0 middle, 1 fine, 2 colour)
         parts = parts & 0xff
         pp = parts[ok]
         for v in np.unique(pp):
             lv = life[pp == v]
-            wv = waits[pp == v]
-            extra = f", waiting {wv.mean():.1f} us ({wv.sum() / lv.sum():.0%})" if wv.any() else ""
-            f1 = field1[pp == v]
-            extra += f", gathering {f1.mean():.1f} us ({f1.sum() / lv.sum():.0%})" if f1.any() else ""
             print(f"     part {v}: {len(lv)} waves, lifetime p50 {np.median(lv):.1f} p90 {np.percentile(lv, 90):.1f}"
-                  f" mean {lv.mean():.1f} us{extra}")
+                  f" mean {lv.mean():.1f} us")
     # per SIMD: waves received, max resident at once, busy span (first start .. last end)
     us, inv = np.unique(simd, return_inverse=True)
     cnt = np.bincount(inv)
@@ -115,7 +109,7 @@ def main():
     assert L.nslam_debug_timeline(buf.ctypes.data, buf.size) == 0
     buf = buf.reshape(3, W, 4).astype(np.int64)
     print(f"mode: prefetch={not args.no_prefetch} serial={args.serial}")
-    analyse("k_query_fwd_parts", buf[0], parts=buf[0][:, 3])
+    analyse("k_query_fwd_units", buf[0], parts=buf[0][:, 3])
     analyse("k_dec_bwd_multi", buf[1], parts=buf[1][:, 3])
     analyse("k_color_wgrad", buf[2])
     # overlap of the three kernels of the last iteration
