@@ -623,6 +623,75 @@ int nslam_tsdf_mc_emit(const float* tsdf, const float* weight, const float* colo
                        const int32_t* vert_off, const int32_t* face_off, int64_t n_verts, int64_t n_faces,
                        double* verts, uint8_t* colors, int32_t* faces, void* stream);
 
+/* Depth odometry against the TSDF volume above (KinectFusion's ray cast and projective point-to-plane ICP;
+ * csrc/nslam_odometry.hip); additive, no ABI bump.  The reference takes its own-data trajectory from open3d's
+ * reconstruction system; the library is absent, so parity with it is unpinned.
+ * Conventions are the volume's: camera +z forward and y down, poses float64 row-major [16] on the HOST (rows 0..2
+ * are read), maps float32 [H][W][3] on the device, an invalid pixel is NaN in all three components.  One stream,
+ * no float atomics: every output is the same from run to run.  Every table, pool and image index is checked
+ * before use, every loop has a fixed trip-count cap, and a pose or value that is not finite ends as an invalid
+ * pixel.  No FMA contraction anywhere.
+ *
+ * nslam_depth_maps, float32: a depth d is valid when d > 0 && d <= depth_trunc (NaN is not).
+ *   xn = ((float)u - cx) / fx,  yn = ((float)v - cy) / fy;  vertex = (xn * d, yn * d, d), NaN when d is invalid
+ *   a = vertex(u + 1, v) - vertex(u, v),  b = vertex(u, v + 1) - vertex(u, v)
+ *   c = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x);  len = sqrtf((c.x c.x + c.y c.y) + c.z c.z)
+ *   n = c / len, negated when (n.x p.x + n.y p.y) + n.z p.z > 0 (p the pixel's vertex: n faces the camera)
+ * The normal is NaN when one of the three depths is invalid, when fabsf(d(u + 1, v) - d) > max_jump or
+ * fabsf(d(u, v + 1) - d) > max_jump, when len is 0 or not finite, and in the last row and the last column.
+ *
+ * nslam_tsdf_raycast, float32, one thread per pixel: table / pool_key / tsdf / weight / n_pool / block_lo /
+ * block_hi / voxel / trunc are the volume's.  m = c2w rounded to float32, L = (float)voxel, B = 16.0f * L,
+ * step = 0.75f * (float)trunc, near / far rounded to float32 (distances along the ray, 0 <= near < far).
+ *   dir = ((m0 xn + m1 yn) + m2) per row, then dir / sqrtf((dir.x^2 + dir.y^2) + dir.z^2);  o = column 3
+ *   samples lie on the lattice t_k = near + (float)k * step, k < 4096, while t_k <= far;  p = o + t * dir
+ * A sample in a block floorf(p / B) that is outside the table or not allocated is invalid, and k advances to
+ * max(k + 1, ceilf((te - near) / step)), te the smallest ((float)(b + 1) * B - o) / dir over the axes with
+ * dir > 0 and ((float)b * B - o) / dir over those with dir < 0: the first lattice sample at or past the
+ * block's exit face.  Otherwise the sample is the trilinear value of the 8 voxel centres around p:
+ *   g = p / L - 0.5f,  i = floorf(g),  f = g - i;  lerp(a, b, f) = a + f * (b - a) along x, then y, then z
+ * valid only if all 8 lie in allocated blocks and have weight > 0.  A valid sample < 0 whose last valid non-zero
+ * sample was > 0 ends the march: a hit when the sample right before it was valid, no hit when an invalid
+ * sample lies between the pair.  A valid sample > 0 after one < 0 (a back face), far and the cap end it with
+ * no hit.  An invalid sample k right after a valid sample > 0 may have stepped over the whole band behind a
+ * surface (it is trunc deep less a voxel for the 8 centres, less than a step): one sample is taken midway, at
+ * near + ((float)k - 0.5f) * step, and a valid value < 0 there is a hit between the two.  For a hit between (tp, fp) and (tc, fc):  ts = tp + (tc - tp) * (fp / (fp - fc));  with fs the
+ * sample at ts, when valid: ts = ts + (tc - ts) * (fs / (fs - fc)) if fs > 0, ts = tp + (ts - tp) * (fp /
+ * (fp - fs)) if fs < 0.  vertex = o + ts * dir (world);  g.c = F(p + L e_c) - F(p - L e_c) of the trilinear
+ * field, normal = g / sqrtf((g.x^2 + g.y^2) + g.z^2): toward increasing TSDF.  Vertex and normal are NaN for no
+ * hit, for an invalid gradient sample and for a zero gradient.  n_pool == 0 is legal (no hit anywhere).
+ *
+ * nslam_icp_sums, float64 from the float32 maps: for every source pixel with u % stride == 0 && v % stride == 0
+ * whose vertex v and normal ns (camera frame, nslam_depth_maps) are not NaN:
+ *   p = ((T0 v.x + T1 v.y) + T2 v.z) + T3 per row of the estimate T;  pc = the same with the model camera's w2c
+ *   reject unless pc.z > 0;  uf = ((pc.x * fx) / pc.z + cx) + 0.5, vf likewise: reject unless 0 <= uf < Wm and
+ *   0 <= vf < Hm;  q, n = the model maps (world frame) at ((int)vf, (int)uf): reject a NaN
+ *   d = p - q: reject unless sqrt((d.x d.x + d.y d.y) + d.z d.z) <= dist_th
+ *   reject unless (rn.x n.x + rn.y n.y) + rn.z n.z >= cos_th, rn = (T0 ns.x + T1 ns.y) + T2 ns.z per row
+ *   r = (n.x d.x + n.y d.y) + n.z d.z;  J = [p.y n.z - p.z n.y, p.z n.x - p.x n.z, p.x n.y - p.y n.x, n]
+ * out float64 [29] = the upper triangle of sum J J^T row by row (21), sum J r (6), sum r r, the inlier count: the
+ * normal equations of T <- exp(xi) T, xi = (rotation, translation).  nslam_icp_partials(Hs, Ws, stride) =
+ * min(ceil(strided pixels / 256), 1024) workgroups: a thread adds its pixels tid, tid + 256 groups, ... in
+ * ascending order, a wave adds its 64 threads by the xor butterfly 32, 16, .. 1, a workgroup its four waves in
+ * wave order and stores 29 partials into partial float64 [n_partial >= groups][29] with plain stores; a second
+ * launch (one wave per sum) adds the workgroups in ascending order.  mask uint8 [Hs][Ws] (or NULL) is zeroed and gets 1 at every
+ * accepted pixel.
+ * NSLAM_EINVAL (before any device call): a null pointer (mask excepted), a size or stride < 1, fx or fy zero,
+ * depth_trunc <= 0, max_jump or dist_th < 0, cos_th outside [-1, 1], near < 0 or far <= near, a T or w2c that
+ * is not finite, voxel / trunc / box as for the volume.  NSLAM_EUNSUPPORTED: 3 H W >= 2^31, 3 * 4096 n_pool >=
+ * 2^31.  NSLAM_EWORKSPACE: n_partial < nslam_icp_partials. */
+int nslam_depth_maps(const float* depth, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                     float depth_trunc, float max_jump, float* vertex, float* normal, void* stream);
+int nslam_tsdf_raycast(const int32_t* table, const int32_t* pool_key, const float* tsdf, const float* weight,
+                       int64_t n_pool, const int32_t* block_lo, const int32_t* block_hi, double voxel, double trunc,
+                       const double* c2w, int32_t H, int32_t W, double fx, double fy, double cx, double cy,
+                       double near, double far, float* vertex, float* normal, void* stream);
+int64_t nslam_icp_partials(int32_t H, int32_t W, int32_t stride);
+int nslam_icp_sums(const float* src_vertex, const float* src_normal, int32_t Hs, int32_t Ws, int32_t stride,
+                   const double* T, const float* model_vertex, const float* model_normal, int32_t Hm, int32_t Wm,
+                   const double* w2c, double fx, double fy, double cx, double cy, double dist_th, double cos_th,
+                   double* partial, int64_t n_partial, double* out, uint8_t* mask, void* stream);
+
 /* Evaluation (src/tools/cull_mesh.py, src/tools/eval_recon.py; csrc/nslam_eval.hip); additive, no ABI bump.
  * No entry point here uses atomics, with one exception: nslam_raster_depth (and the replay's nslam_scene_render on
  * the same passes) combines its hits with an integer atomicMin, which does not depend on the order.  Every output

@@ -8,7 +8,7 @@ The directory name is not a Python identifier: import with importlib.import_modu
 import sys as _sys
 
 from . import _lib, common, datasets, decoder, distributed, engine, evaluation, mapper, mesher, ops, packing, renderer, slam, tracker  # noqa: F401,E501
-from . import config, logger, nice_slam, replay, tsdf, visualizer  # noqa: F401
+from . import config, logger, nice_slam, odometry, replay, tsdf, visualizer  # noqa: F401
 from .datasets import get_dataset  # noqa: F401
 from .decoder import NICE, MLP, MLP_no_xyz  # noqa: F401
 from .logger import Logger  # noqa: F401
@@ -23,4 +23,4 @@ _sys.modules.setdefault("nice_slam_amd", _sys.modules[__name__])
 
 __all__ = ["NICE", "MLP", "MLP_no_xyz", "Renderer", "Tracker", "Mapper", "Mesher", "get_dataset", "common", "datasets",
            "decoder", "distributed", "evaluation", "mapper", "mesher", "ops", "packing", "renderer", "slam", "tracker",
-           "NICE_SLAM", "Logger", "Visualizer", "config", "logger", "nice_slam", "visualizer", "replay", "tsdf"]
+           "NICE_SLAM", "Logger", "Visualizer", "config", "logger", "nice_slam", "visualizer", "replay", "tsdf", "odometry"]

@@ -170,6 +170,8 @@ EXPORTS = (
     # TSDF fusion: block range, touch masks, integration, marching cubes over the pool (additive: no ABI bump)
     "nslam_tsdf_block_range", "nslam_tsdf_touch", "nslam_tsdf_integrate", "nslam_tsdf_mc_count",
     "nslam_tsdf_mc_emit",
+    # depth odometry: depth maps, the volume's ray cast, ICP sums (additive: no ABI bump)
+    "nslam_depth_maps", "nslam_tsdf_raycast", "nslam_icp_partials", "nslam_icp_sums",
 )
 
 _lib = None
@@ -307,6 +309,13 @@ def lib():
         L.nslam_tsdf_mc_count.argtypes = [vp, vp, vp, i64, vp, i32p, i32p, vp, vp, vp]
         L.nslam_tsdf_mc_emit.argtypes = [vp, vp, vp, i64, vp, i64, vp, i32p, i32p, f64, vp, vp, vp, vp, i64, i64, vp,
                                          vp, vp, vp]
+        L.nslam_depth_maps.argtypes = [vp, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp, vp]
+        L.nslam_tsdf_raycast.argtypes = [vp, vp, vp, vp, i64, i32p, i32p, f64, f64, dp, i32, i32, f64, f64, f64, f64,
+                                         f64, f64, vp, vp, vp]
+        L.nslam_icp_partials.argtypes = [i32, i32, i32]
+        L.nslam_icp_partials.restype = i64
+        L.nslam_icp_sums.argtypes = [vp, vp, i32, i32, i32, dp, vp, vp, i32, i32, dp, f64, f64, f64, f64, f64, f64,
+                                     vp, i64, vp, vp, vp]
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L

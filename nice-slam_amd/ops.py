@@ -1862,3 +1862,90 @@ def tsdf_marching_cubes(tsdf, weight, color_pool, pool_key, n_pool, table, block
                                   n_verts, n_faces, ptr(verts), ptr(colors), ptr(faces), stream_ptr(dev))
     check(rc, "nslam_tsdf_mc_emit")
     return verts, faces, colors
+
+
+# ------------------------------------------------------------------------------------------------
+# depth odometry (csrc/nslam_odometry.hip); the tracker itself is odometry.DepthOdometry
+# ------------------------------------------------------------------------------------------------
+def _pose16(m, name):
+    """A 4x4 pose (tensor or array) as the HOST float64 [16] the odometry entry points read."""
+    if isinstance(m, torch.Tensor):
+        m = m.detach().cpu().tolist()
+    flat = [float(x) for row in m for x in row]
+    if len(flat) != 16:
+        raise ValueError(f"{name}: a 4x4 matrix expected")
+    return (ctypes.c_double * 16)(*flat)
+
+
+def depth_maps(depth, fx, fy, cx, cy, depth_trunc, max_jump):
+    """nslam_depth_maps → (vertex, normal) float32 [H,W,3] in the camera frame (+z forward), NaN where invalid.
+
+    depth float32 [H,W]."""
+    _want(depth, "depth", torch.float32, (None, None))
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    if H < 1 or W < 1:
+        raise ValueError("depth_maps: an empty image")
+    dev = depth.device
+    vertex = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    normal = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    rc = lib().nslam_depth_maps(ptr(depth), H, W, float(fx), float(fy), float(cx), float(cy), float(depth_trunc),
+                                float(max_jump), ptr(vertex), ptr(normal), stream_ptr(dev))
+    check(rc, "nslam_depth_maps")
+    return vertex, normal
+
+
+def tsdf_raycast(table, pool_key, tsdf, weight, n_pool, block_lo, block_hi, voxel, trunc, c2w, H, W, fx, fy, cx, cy,
+                 near, far):
+    """nslam_tsdf_raycast over the first n_pool blocks → (vertex, normal) float32 [H,W,3] in the world frame, NaN
+    where a ray hits nothing.  c2w: a 4x4 pose (+z forward), read on the host."""
+    cap, n_pool = int(tsdf.shape[0]), int(n_pool)
+    if not 0 <= n_pool <= cap:
+        raise ValueError("tsdf_raycast: n_pool exceeds the pool's capacity")
+    _want(tsdf, "tsdf", torch.float32, (cap, 4096))
+    _want(weight, "weight", torch.float32, (cap, 4096))
+    _want(pool_key, "pool_key", torch.int32, (None,))
+    if int(pool_key.shape[0]) < n_pool:
+        raise ValueError("tsdf_raycast: pool_key is shorter than the pool")
+    lo, hi = _i3(block_lo, "block_lo"), _i3(block_hi, "block_hi")
+    cells = max(0, hi[0] - lo[0]) * max(0, hi[1] - lo[1]) * max(0, hi[2] - lo[2])
+    _want(table, "table", torch.int32, (cells,))
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError("tsdf_raycast: an empty image")
+    dev = table.device
+    vertex = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    normal = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    rc = lib().nslam_tsdf_raycast(ptr(table), ptr(pool_key), ptr(tsdf), ptr(weight), n_pool, lo, hi, float(voxel),
+                                  float(trunc), _pose16(c2w, "c2w"), H, W, float(fx), float(fy), float(cx), float(cy),
+                                  float(near), float(far), ptr(vertex), ptr(normal), stream_ptr(dev))
+    check(rc, "nslam_tsdf_raycast")
+    return vertex, normal
+
+
+def icp_sums(src_vertex, src_normal, T, model_vertex, model_normal, w2c, fx, fy, cx, cy, stride, dist_th, cos_th,
+             return_mask=False):
+    """nslam_icp_sums → float64 [29] on the device: the upper triangle of sum J J^T (21), sum J r (6), sum r^2 and
+    the inlier count of the projective point-to-plane association (with return_mask also uint8 [Hs,Ws]: the
+    accepted source pixels).
+
+    src_* float32 [Hs,Ws,3] (camera frame); model_* float32 [Hm,Wm,3] (world frame, seen by the camera whose
+    world-to-camera matrix is w2c); T, w2c: 4x4 poses read on the host."""
+    _want(src_vertex, "src_vertex", torch.float32, (None, None, 3))
+    Hs, Ws = int(src_vertex.shape[0]), int(src_vertex.shape[1])
+    _want(src_normal, "src_normal", torch.float32, (Hs, Ws, 3))
+    _want(model_vertex, "model_vertex", torch.float32, (None, None, 3))
+    Hm, Wm = int(model_vertex.shape[0]), int(model_vertex.shape[1])
+    _want(model_normal, "model_normal", torch.float32, (Hm, Wm, 3))
+    if min(Hs, Ws, Hm, Wm) < 1 or int(stride) < 1:
+        raise ValueError("icp_sums: non-empty maps and stride >= 1 expected")
+    dev = src_vertex.device
+    groups = int(lib().nslam_icp_partials(Hs, Ws, int(stride)))
+    partial = torch.empty(groups, 29, dtype=torch.float64, device=dev)
+    out = torch.empty(29, dtype=torch.float64, device=dev)
+    mask = torch.empty(Hs, Ws, dtype=torch.uint8, device=dev) if return_mask else None
+    rc = lib().nslam_icp_sums(ptr(src_vertex), ptr(src_normal), Hs, Ws, int(stride), _pose16(T, "T"),
+                              ptr(model_vertex), ptr(model_normal), Hm, Wm, _pose16(w2c, "w2c"), float(fx), float(fy),
+                              float(cx), float(cy), float(dist_th), float(cos_th), ptr(partial), groups, ptr(out),
+                              ptr(mask), stream_ptr(dev))
+    check(rc, "nslam_icp_sums")
+    return (out, mask) if return_mask else out

@@ -173,6 +173,19 @@ class TSDFVolume(object):
                                           self.table, self.block_lo, self.block_hi, self.voxel_length)
         return {"vertices": v, "faces": f, "colors": c}
 
+    def raycast(self, c2w, H, W, fx, fy, cx, cy, near, far):
+        """The volume seen from the pose c2w [4,4] (+z forward; tensor or array) by an H x W pinhole camera
+        (nslam_tsdf_raycast) → (vertex, normal) device float32 [H,W,3] in the world frame: the zero crossing of
+        every pixel's ray between the distances near and far along it, and the TSDF's gradient direction there
+        (toward the free side).  NaN where a ray hits nothing."""
+        if isinstance(c2w, torch.Tensor):
+            c2w = c2w.detach().cpu().numpy()
+        c2w = np.asarray(c2w, dtype=np.float64)
+        if c2w.shape != (4, 4):
+            raise ValueError("c2w: [4,4] expected")
+        return ops.tsdf_raycast(self.table, self._key, self._tsdf, self._weight, self.n_blocks, self.block_lo,
+                                self.block_hi, self.voxel_length, self.sdf_trunc, c2w, H, W, fx, fy, cx, cy, near, far)
+
     # the pool's live part (views): [n_blocks,4096] (x * 16 + y) * 16 + z within a block; colour [3,n_blocks,4096]
     @property
     def tsdf(self):
