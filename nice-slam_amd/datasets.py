@@ -38,6 +38,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import ops
+
 
 def _read_color(path):
     from PIL import Image
@@ -144,8 +146,7 @@ class BaseDataset(torch.utils.data.Dataset):
         u8 = u8.to(self.device, non_blocking=non_blocking)
         if self.distortion is not None:  # datasets.py:85-88: the colour image only, before /255
             if u8.is_cuda:  # (this stream: the side stream under prefetch)
-                from .ops import undistort_u8 as undistort_dev
-                u8 = undistort_dev(u8.contiguous(), self.fx, self.fy, self.cx, self.cy, self.distortion)
+                u8 = ops.undistort_u8(u8.contiguous(), self.fx, self.fy, self.cx, self.cy, self.distortion)
             else:
                 u8 = torch.from_numpy(undistort_u8(u8.numpy(), self.fx, self.fy, self.cx, self.cy, self.distortion))
         color = self._lut(u8.device)[u8.long()]

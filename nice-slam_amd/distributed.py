@@ -12,6 +12,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from . import ops
+
 
 def _collectives(group, force: bool) -> bool:
     """Whether an exchange issues its collectives: world > 1, or `force` with an initialised process
@@ -91,7 +93,6 @@ class SparseGradExchange:
     """
 
     def __init__(self, engine, rows, group=None, pack=None, unpack=None, force_collectives=False):
-        from . import ops
         self.engine, self.group = engine, group
         self.force = force_collectives
         self.pack = pack or ops.rows_pack
@@ -168,8 +169,7 @@ class SparseGradExchange:
         for g, off in tails:
             self.pack(None, None, g.reshape(-1), buf[off:off + g.numel()])
         if _collectives(self.group, self.force):
-            from .ops import _span
-            with _span("collective.all_reduce"):
+            with ops.span("collective.all_reduce"):
                 dist.all_reduce(buf, group=self.group)
         if rows.numel():
             self.unpack(buf, rows, gbuf, None)
@@ -217,7 +217,6 @@ class ShardedAdamExchange:
 
     def __init__(self, engine, optimizer, group=None, group_dec=None, pack=None, unpack=None, adam_slices=None,
                  force_collectives=False):
-        from . import ops
         self.engine, self.opt, self.group = engine, optimizer, group
         init = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size(group) if init else 1
@@ -284,8 +283,7 @@ class ShardedAdamExchange:
         own = span[self.rank * chunk:(self.rank + 1) * chunk]
         if not self.coll:
             return own
-        from .ops import _span
-        with _span("collective.reduce_scatter"):
+        with ops.span("collective.reduce_scatter"):
             if dist.get_backend(group) == "gloo":
                 dist.all_reduce(span, group=group)
             else:
@@ -296,8 +294,7 @@ class ShardedAdamExchange:
         if not self.coll:
             return
         own = vals[self.rank * chunk:(self.rank + 1) * chunk]
-        from .ops import _span
-        with _span("collective.all_gather"):
+        with ops.span("collective.all_gather"):
             if dist.get_backend(group) == "gloo":
                 parts = list(vals.split(chunk))
                 dist.all_gather(parts, own.clone(), group=group)

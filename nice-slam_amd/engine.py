@@ -105,7 +105,7 @@ def _dec_table(names, ptr_of):
     """(4-slot pointer table indexed by NSLAM_DEC_*, bit mask of `names`): slot of a name = ptr_of(name)."""
     tab, mask = (ctypes.c_void_p * 4)(), 0
     for name in names:
-        d = ops._DEC_ID[name]
+        d = ops.DEC_ID[name]
         mask |= 1 << d
         tab[d] = ptr_of(name)
     return tab, mask
@@ -114,7 +114,7 @@ def _dec_table(names, ptr_of):
 def _live_tables(decs, names, idx, nl):
     """The tables of `names` into live_lists' (idx [decoders of the stage `decs`, N*S], nl [4]), and their mask."""
     ips, mask = _dec_table(names, lambda name: idx[decs.index(name)].data_ptr())
-    return ips, _dec_table(names, lambda name: nl[ops._DEC_ID[name]:].data_ptr())[0], mask
+    return ips, _dec_table(names, lambda name: nl[ops.DEC_ID[name]:].data_ptr())[0], mask
 
 
 @dataclasses.dataclass
@@ -241,8 +241,8 @@ class MappingEngine:
         self.device = torch.device(device)
         names = [n for n in ("coarse", "middle", "fine", "color") if hasattr(nice, n + "_decoder")]
         self.decs = {n: FlatDecoder(nice.decoder(n)) for n in names}
-        self.dec_bounds = {n: ops._bound_list(nice.decoder(n).bound) for n in names}
-        self.oob = ops._bound_list(bound)
+        self.dec_bounds = {n: ops.bound_list(nice.decoder(n).bound) for n in names}
+        self.oob = ops.bound_list(bound)
         self._saved = None  # ReLU masks of the last query_fwd (read by query_bwd)
         self._tape = None   # colour-decoder activation tape of the last query_fwd (ABI v9)
         self.occ_add = None  # middle occupancy of the last deferred-combine query_fwd
@@ -378,17 +378,17 @@ class MappingEngine:
     def _cfg(self, stage, ro, rd, z, grid_grads, dec_grads, masks=None, tape=None):
         """The query descriptor of a ray batch; masks / tape: the forward's ReLU masks and activation tape
         (written by query_fwd, read by query_bwd; live_lists needs neither)."""
-        decs = ops._DEC_FOR_STAGE[stage]
+        decs = ops.DEC_FOR_STAGE[stage]
         meta = ops.QueryMeta(stage, decs, {n: self.decs[n].packer for n in decs},
                              {n: self.dec_bounds[n] for n in decs}, self.oob, None)
         pairs = [(None, None, None)] * 4
         for n in decs:
             key = _GRID_OF[n]
             gg = key in grid_grads
-            pairs[ops._DEC_ID[n]] = (self.c[key], self.ggrad[key] if gg else None, self.slot.get(key) if gg else None)
+            pairs[ops.DEC_ID[n]] = (self.c[key], self.ggrad[key] if gg else None, self.slot.get(key) if gg else None)
         packed = {n: self.decs[n].packed for n in decs}
         dg = {n: self.decs[n].grad for n in decs if n in dec_grads}
-        cfg = ops._fill_cfg(meta, pairs, packed, dg, False)
+        cfg = ops.fill_cfg(meta, pairs, packed, dg, False)
         cfg.rays_o, cfg.rays_d, cfg.z_vals, cfg.n_samples = ptr(ro), ptr(rd), ptr(z), z.shape[1]
         cfg.saved_masks = ptr(masks)
         cfg.act_tape = ptr(tape)
@@ -399,7 +399,7 @@ class MappingEngine:
         against the current slot maps (nslam_live_points), on the current stream: per decoder the ascending
         indices of the points with a frustum-selected corner in its grid and their count.  Valid until a
         slot map changes (set_rows, bind_masks).  out: (live_idx, n_live) to write into."""
-        decs = ops._DEC_FOR_STAGE[stage]
+        decs = ops.DEC_FOR_STAGE[stage]
         n = z.numel()
         if out is None:
             out = (torch.empty(len(decs), n, dtype=torch.int32, device=z.device),
@@ -410,7 +410,7 @@ class MappingEngine:
         ips, nps, mask = _live_tables(decs, decs, idx, nl)
         wsb = lib().nslam_live_points_workspace_size(n)
         ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=z.device)
-        with ops._span("live_points"):
+        with ops.span("live_points"):
             rc = lib().nslam_live_points(ctypes.byref(cfg), mask, None, n, ips, nps, ptr(ws), wsb, stream_ptr(z.device))
         check(rc, "nslam_live_points")
         return idx, nl
@@ -456,7 +456,7 @@ class MappingEngine:
         live = None if pts_grad else live
         cfg = self._cfg(stage, ro, rd, z, grid_grads, dec_grads, masks=self._saved, tape=self._tape)
         cfg.need_pts_grad = int(bool(pts_grad))
-        decs = list(ops._DEC_FOR_STAGE[stage])
+        decs = list(ops.DEC_FOR_STAGE[stage])
         plan = backward_plan(decs, dec_grads, masks=self._saved is not None, tape=self._tape is not None, n=n,
                              merge=self.merge, wgrad_first=self.wgrad_first, adam_merge=self.adam_merge,
                              concurrent=self.concurrent if concurrent is None else concurrent,
@@ -471,7 +471,7 @@ class MappingEngine:
         if plan.merge_adam and self._wg_ev is None:
             self._wg_ev = torch.cuda.Event()
         wgrad_st = None
-        with ops._span("query_bwd"):
+        with ops.span("query_bwd"):
             for st in streams[1:]:  # fork: every branch starts from the same point of the main stream
                 st.wait_stream(main)
                 for t in (ro, rd, z, g_raw, self._saved, self._tape) + (tuple(live) if live else ()):
@@ -533,7 +533,7 @@ class MappingEngine:
     def _launch_wgrad(self, cfg, n, g_raw, st):
         wsb = lib().nslam_query_bwd_decoder_workspace_size(ctypes.byref(cfg), _lib.DEC_COLOR, n)
         ws = torch.empty(wsb, dtype=torch.uint8, device=g_raw.device)
-        with ops._span("query_bwd.color_wgrad"):
+        with ops.span("query_bwd.color_wgrad"):
             rc = lib().nslam_color_wgrad(ctypes.byref(cfg), None, n, ptr(g_raw), ptr(ws), wsb, st.cuda_stream)
         check(rc, "nslam_color_wgrad")
 
@@ -541,8 +541,8 @@ class MappingEngine:
         """gp: {decoder: its d/dpts buffer} (plain form); live: live_lists() of the batch (live-point form)."""
         lc = _lib.NslamQueryCfg.from_buffer_copy(cfg)  # grids (and d/dpts) only
         for name in names:
-            lc.dgrad[ops._DEC_ID[name]] = _lib.NslamDecGrad()
-        with ops._span("query_bwd." + "+".join(names)):
+            lc.dgrad[ops.DEC_ID[name]] = _lib.NslamDecGrad()
+        with ops.span("query_bwd." + "+".join(names)):
             if live is not None:
                 ips, nps, mask = _live_tables(decs, names, *live)
                 rc = lib().nslam_query_bwd_decoders_live(ctypes.byref(lc), mask, None, n, ptr(g_raw), ips, nps,
@@ -554,10 +554,10 @@ class MappingEngine:
         check(rc, "nslam_query_bwd_decoders")
 
     def _launch_one(self, cfg, name, n, g_raw, st, gp=None):
-        d = ops._DEC_ID[name]
+        d = ops.DEC_ID[name]
         wsb = lib().nslam_query_bwd_decoder_workspace_size(ctypes.byref(cfg), d, n)
         ws = torch.empty(wsb, dtype=torch.uint8, device=g_raw.device) if wsb else None
-        with ops._span("query_bwd." + name):
+        with ops.span("query_bwd." + name):
             rc = lib().nslam_query_bwd_decoder(ctypes.byref(cfg), d, 0, None, n, ptr(g_raw),
                                                ptr(gp[name]) if gp else None, ptr(ws), wsb, st.cuda_stream)
         check(rc, "nslam_query_bwd_decoder")
@@ -572,7 +572,7 @@ class MappingEngine:
 
     def grads_for(self, stage, trainable_decoders):
         """(grid keys, decoder names) that receive gradients in `stage` (Mapper.py:335-341)."""
-        decs = ops._DEC_FOR_STAGE[stage]
+        decs = ops.DEC_FOR_STAGE[stage]
         keys = tuple(_GRID_OF[n] for n in decs)
         return keys, tuple(n for n in decs if n in trainable_decoders)
 

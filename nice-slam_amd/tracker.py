@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import common as _common
+from . import ops
 from .common import (camera_tensors, constant_speed_guess, get_camera_from_tensor, get_samples,
                      get_tensor_from_camera, inside_mask, pose4)
 
@@ -136,9 +137,8 @@ class Tracker(object):
         """TrackingEngine over the current decoder/grid snapshot."""
         if self._engine is None:
             from .engine import TrackingEngine
-            from .ops import channels_last
             r = self.renderer
-            c = {k: channels_last(v) for k, v in self.c.items() if k != "grid_coarse"}
+            c = {k: ops.channels_last(v) for k, v in self.c.items() if k != "grid_coarse"}
             self._engine = TrackingEngine(self.decoders, c, self.bound, r.N_samples, r.N_surface, (self.H, self.W),
                                           (self.fx, self.fy, self.cx, self.cy),
                                           ignore_edge=(self.ignore_edge_H, self.ignore_edge_W),
@@ -262,11 +262,10 @@ class Tracker(object):
         kernel and the whole loop is ONE hipGraph, captured on the first frame and replayed on every
         later one (the frame is copied into persistent slots; a fresh Adam per frame by resetting its
         state).  With a generator (pinned draws): torch.randint per iteration, eager."""
-        from .ops import FusedAdam
         eng = self.engine()
         device = self.device
         cam = camera_tensor.detach().clone().requires_grad_(True)
-        opt = FusedAdam([{"params": [cam], "lr": self.cam_lr}])
+        opt = ops.FusedAdam([{"params": [cam], "lr": self.cam_lr}])
         best = cam.detach().clone()
         best_loss = torch.full((), float("inf"), dtype=torch.float64, device=device)
         depth = gt_depth.float().contiguous()
@@ -283,8 +282,6 @@ class Tracker(object):
         guess (constant speed, Tracker.py:191-198), its camera 7-vector, a fresh Adam, the camera loop with
         device pixel draws and the device-side best-pose selection (Tracker.py:225-250), and the result pose.
         Per frame the host copies the frame and the previous poses into persistent buffers and replays."""
-        from . import ops
-        from .ops import FusedAdam
         eng = self.engine()
         dev = self.device
         st = self._fstate
@@ -295,7 +292,7 @@ class Tracker(object):
                 "depth": torch.zeros(self.H, self.W, dtype=torch.float32, device=dev),
                 "color": torch.zeros(self.H, self.W, 3, dtype=torch.float32, device=dev),
                 "pre": torch.eye(4, dtype=torch.float32, device=dev), "prev2": torch.eye(4, dtype=torch.float32, device=dev),
-                "cam": cam, "opt": FusedAdam([{"params": [cam], "lr": self.cam_lr}]),
+                "cam": cam, "opt": ops.FusedAdam([{"params": [cam], "lr": self.cam_lr}]),
                 "best": torch.zeros(7, dtype=torch.float32, device=dev),
                 "best_loss": torch.zeros((), dtype=torch.float64, device=dev), "out": out}
             st["opt"].init_state()

@@ -68,13 +68,27 @@ def test_no_cpu_fallback(pkg):
         pkg.ops.composite(torch.zeros(2, 4, 4), torch.zeros(2, 4, dtype=torch.float64))
 
 
+# the C name(s) of every ctypes mirror in _lib.py (nslam_imap_grads has nslam_imap_params' layout and one mirror)
+_C_STRUCTS = {
+    "NslamGrid": ("nslam_grid",), "NslamDecGrad": ("nslam_dec_grad",), "NslamQueryCfg": ("nslam_query_cfg",),
+    "NslamFrame": ("nslam_frame",), "NslamLossCfg": ("nslam_loss_cfg",), "NslamAdamSeg": ("nslam_adam_seg",),
+    "NslamDraw": ("nslam_draw",), "NslamCamTail": ("nslam_cam_tail",), "NslamCamTailLr2": ("nslam_cam_tail_lr2",),
+    "NslamImapParams": ("nslam_imap_params", "nslam_imap_grads"), "NslamImapQuery": ("nslam_imap_query",),
+}
+
+
 def test_struct_layouts_match_header(pkg, tmp_path):
     """sizeof/offsetof of every ABI struct, compiled by gcc from include/nslam.h, equal the ctypes
-    mirrors in _lib.py."""
+    mirrors in _lib.py: every ctypes.Structure the module defines, under each C name it mirrors."""
     L = pkg._lib
-    structs = {"nslam_grid": L.NslamGrid, "nslam_dec_grad": L.NslamDecGrad, "nslam_query_cfg": L.NslamQueryCfg,
-               "nslam_frame": L.NslamFrame, "nslam_loss_cfg": L.NslamLossCfg, "nslam_adam_seg": L.NslamAdamSeg,
-               "nslam_draw": L.NslamDraw}
+    mirrors = {n: c for n, c in vars(L).items() if isinstance(c, type) and issubclass(c, ctypes.Structure)
+               and c.__module__ == L.__name__}
+    assert set(mirrors) == set(_C_STRUCTS), "a ctypes mirror in _lib.py without its C name here (or the reverse)"
+    structs = {cname: mirrors[n] for n, cnames in _C_STRUCTS.items() for cname in cnames}
+    assert len(structs) == 12 and {"nslam_grid", "nslam_dec_grad", "nslam_query_cfg", "nslam_frame", "nslam_loss_cfg",
+                                   "nslam_adam_seg", "nslam_draw"} <= set(structs)
+    header = open(os.path.join(REPO, "include", "nslam.h")).read()
+    assert set(re.findall(r"^\} *(nslam_\w+);", header, re.M)) == set(structs)  # every struct typedef of the header
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nslam.h"', "int main(void) {"]
     for cname, py in structs.items():
         lines.append(f'  printf("{cname} size %zu\\n", sizeof({cname}));')
@@ -91,6 +105,15 @@ def test_struct_layouts_match_header(pkg, tmp_path):
         assert got[(cname, "size")] == ctypes.sizeof(py), cname
         for f in py._fields_:
             assert got[(cname, f[0])] == getattr(py, f[0]).offset, (cname, f[0])
+
+
+def test_every_export_has_a_declared_signature(pkg):
+    """After lib() has bound, every export has argtypes set (nslam_abi_version takes none): an export without
+    them would be called with ctypes' default conversions."""
+    L = pkg._lib.lib()
+    for name in pkg._lib.EXPORTS:
+        if name != "nslam_abi_version":
+            assert getattr(L, name).argtypes is not None, name
 
 
 def test_v4_entry_points_validate_without_gpu(pkg):

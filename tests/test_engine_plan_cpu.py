@@ -44,12 +44,12 @@ def test_backward_plan_table(case, over, units, streams, merge_adam):
 
 
 def test_stage_decoders_are_the_tables():
-    """The decs the table passes are the stages' (ops._DEC_FOR_STAGE)."""
+    """The decs the table passes are the stages' (ops.DEC_FOR_STAGE)."""
     ops = importlib.import_module("nice-slam_amd.ops")
-    assert tuple(ops._DEC_FOR_STAGE["color"]) == (M, F, C)
-    assert tuple(ops._DEC_FOR_STAGE["fine"]) == (M, F)
-    assert tuple(ops._DEC_FOR_STAGE["middle"]) == (M,)
-    assert tuple(ops._DEC_FOR_STAGE["coarse"]) == ("coarse",)
+    assert tuple(ops.DEC_FOR_STAGE["color"]) == (M, F, C)
+    assert tuple(ops.DEC_FOR_STAGE["fine"]) == (M, F)
+    assert tuple(ops.DEC_FOR_STAGE["middle"]) == (M,)
+    assert tuple(ops.DEC_FOR_STAGE["coarse"]) == ("coarse",)
 
 
 @pytest.mark.parametrize("var", ["NSLAM_LIVE_POINTS", "NSLAM_ADAM_MERGE", "NSLAM_WGRAD_FIRST", "NSLAM_PREFETCH_STREAM"])

@@ -1,4 +1,4 @@
-"""The enqueue trace of an engine iteration: which ops._span opens on which stream, in which order.
+"""The enqueue trace of an engine iteration: which ops.span opens on which stream, in which order.
 
 A recorder stands in for ops.TIMER; every span appends (name, label), label = "main" for the stream current
 when the case started and "side0", "side1", ... for the others in order of first appearance.  Callbacks the

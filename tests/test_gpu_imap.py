@@ -83,7 +83,7 @@ def test_packed_fragments_match_layout():
     L = P._lib.lib()
     assert L.nslam_imap_packed_size() == 4 * P.packing.IMAP_PACKED
     packed = torch.empty(P.packing.IMAP_PACKED, dtype=torch.float32, device=DEV)
-    s = P.ops._imap_struct(ps[0], ps[1:9:2], ps[2:9:2], ps[9], ps[10])
+    s = P.ops.imap_struct(ps[0], ps[1:9:2], ps[2:9:2], ps[9], ps[10])
     import ctypes
     P._lib.check(L.nslam_imap_pack(ctypes.byref(s), packed.data_ptr(), P._lib.stream_ptr(DEV)), "pack")
     want = P.packing.imap_fragments([sd[f"pts_linears.{i}.weight"] for i in range(4)])

@@ -85,7 +85,7 @@ def test_live_lists_match_torch(tiny, nf, n_per):
     torch.cuda.synchronize()
     some_dead = False
     for i, name in enumerate(("middle", "fine", "color")):
-        k = int(nl[P.ops._DEC_ID[name]])
+        k = int(nl[P.ops.DEC_ID[name]])
         assert 0 <= k <= n, name
         lst = idx[i, :k].long()
         assert bool((lst[1:] > lst[:-1]).all()), f"{name}: not ascending"
@@ -125,7 +125,7 @@ def test_live_edge_cases(tiny):
     g_raw = torch.randn(n, 4, device=DEV, generator=torch.Generator(device=DEV).manual_seed(2))
     idx, nl = eng.live_lists("color", ro, rd, z)
     for i, name in enumerate(("middle", "fine", "color")):
-        assert int(nl[P.ops._DEC_ID[name]]) == n, name
+        assert int(nl[P.ops.DEC_ID[name]]) == n, name
         assert torch.equal(idx[i].long(), torch.arange(n, device=DEV)), name
     off = _bwd(eng, "color", ro, rd, z, g_raw, False, KEYS)
     on = _bwd(eng, "color", ro, rd, z, g_raw, True, KEYS)
@@ -138,7 +138,7 @@ def test_live_edge_cases(tiny):
     eng.rows_gen += 1
     idx, nl = eng.live_lists("color", ro, rd, z)
     for name in ("middle", "fine", "color"):
-        assert int(nl[P.ops._DEC_ID[name]]) == 0, name
+        assert int(nl[P.ops.DEC_ID[name]]) == 0, name
     eng.gall.zero_()
     eng.query_fwd("color", ro, rd, z, defer_occ=True)
     eng.query_bwd("color", ro, rd, z, g_raw, KEYS, (), live=(idx, nl))

@@ -225,12 +225,12 @@ def fwd_ws(nice, grids, stage, pts, bound, split, defer):
     """nslam_query_fwd_ws (split) or nslam_query_fwd in pts form → (raw, deferred middle occupancy or None,
     saved masks, tape or None)."""
     ops, lib = P.ops, P._lib.lib()
-    decs = ops._DEC_FOR_STAGE[stage]
+    decs = ops.DEC_FOR_STAGE[stage]
     packers = {d: nice.decoder(d).packer() for d in decs}
-    meta = ops.QueryMeta(stage, decs, packers, {d: ops._bound_list(nice.decoder(d).bound) for d in decs},
-                         ops._bound_list(bound), None)
+    meta = ops.QueryMeta(stage, decs, packers, {d: ops.bound_list(nice.decoder(d).bound) for d in decs},
+                         ops.bound_list(bound), None)
     packed = {d: packers[d].pack(list(nice.decoder(d).parameters())) for d in decs}
-    cfg = ops._fill_cfg(meta, [(grids[k], None) for k in GRID_KEYS], packed, {}, False)
+    cfg = ops.fill_cfg(meta, [(grids[k], None) for k in GRID_KEYS], packed, {}, False)
     n = pts.shape[0]
     saved = torch.zeros(lib.nslam_query_saved_size(n), dtype=torch.uint8, device=DEV)
     cfg.saved_masks = saved.data_ptr()
@@ -258,7 +258,7 @@ def test_forward_variants(fx, scene, stage):
                    fx[case + ".floor_max.raw"], fails)
     assert not fails, "\n".join(fails)
     nt = (sc.M + 31) // 32
-    decs = [P.ops._DEC_ID[d] for d in P.ops._DEC_FOR_STAGE[stage]]
+    decs = [P.ops.DEC_ID[d] for d in P.ops.DEC_FOR_STAGE[stage]]
     masks = lambda s: s.view(torch.int16).view(4, nt, 5, 64)[decs]  # noqa: E731  [decoder][tile][layer][lane]
     assert int((masks(base[2]) != 0).sum()) > 0
     for split, defer in ((True, False), (True, True), (False, False)):
@@ -349,7 +349,7 @@ def test_live_point_backward(fx, scene, ray_ref, stage):
     eng.gall.zero_()
     eng.query_bwd(stage, ro, rd, z, g_raw, keys, (), live=live)
     torch.cuda.synchronize()
-    n_live = [int(live[1][P.ops._DEC_ID[d]]) for d in P.ops._DEC_FOR_STAGE[stage]]
+    n_live = [int(live[1][P.ops.DEC_ID[d]]) for d in P.ops.DEC_FOR_STAGE[stage]]
     print("live points per decoder:", n_live, "of", z.numel())
     assert all(0 < k <= z.numel() for k in n_live) and any(k < z.numel() for k in n_live)
     fails = []
@@ -405,7 +405,7 @@ def test_mapping_iteration_and_adam_mirror(scene, stage):
     frames = [one_frame(scene, 201)]
     fdev = [tuple(t.to(DEV) for t in f) for f in frames]
     pix = torch.randint(CAM["H"] * CAM["W"], (N_PIX,), generator=torch.Generator().manual_seed(202))
-    trainable = P.ops._DEC_FOR_STAGE[stage]
+    trainable = P.ops.DEC_FOR_STAGE[stage]
     intr = (CAM["fx"], CAM["fy"], CAM["cx"], CAM["cy"])
 
     def setup():

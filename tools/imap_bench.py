@@ -80,10 +80,10 @@ def stage_launches(args):
     z = torch.sort(torch.rand(args.rays, S, dtype=torch.float64, device=dev) * gt[:, None].double() * 1.2, -1)[0] + 0.01
     pts = (ro[:, None, :] + rd[:, None, :] * z[..., None]).reshape(-1, 3).contiguous()
     ps = [p.detach().contiguous() for p in ops.imap_params(dec)]
-    st = ops._imap_struct(ps[0], ps[1:9:2], ps[2:9:2], ps[9], ps[10])
+    st = ops.imap_struct(ps[0], ps[1:9:2], ps[2:9:2], ps[9], ps[10])
     grads = [torch.zeros_like(p) for p in ps]
-    gs = ops._imap_struct(grads[0], grads[1:9:2], grads[2:9:2], grads[9], grads[10])
-    q = ops._imap_query_struct(pts, None, ops._bound_list(bound))
+    gs = ops.imap_struct(grads[0], grads[1:9:2], grads[2:9:2], grads[9], grads[10])
+    q = ops.imap_query_struct(pts, None, ops.bound_list(bound))
     packed = torch.empty(L.nslam_imap_packed_size() // 4, dtype=torch.float32, device=dev)
     raw = torch.empty(n, 4, dtype=torch.float32, device=dev)
     tape = torch.empty(L.nslam_imap_tape_size(n) // 4, dtype=torch.float32, device=dev)
