@@ -514,7 +514,14 @@ size_t nslam_point_masks_workspace_size(int64_t n, int32_t n_frames, int64_t poi
  * Pass 2 writes verts float64 [n_verts][3] = origin + (index + t) * spacing with t = (level - a) / (b - a) in
  * float32 along the crossing edge, and faces int32 [n_faces][3] (vertex ids), vertices in owner-edge order,
  * faces in cell order.  Face normals (right-hand rule) point toward decreasing field values.  The case
- * table is csrc/nslam_mc_table.h (tools/gen_mc_table.py).  NSLAM_EUNSUPPORTED when 3 N >= 2^31. */
+ * table is csrc/nslam_mc_table.h (tools/gen_mc_table.py); a cell's triangles are the table's loops in the
+ * table's winding, each fanned from the apex that csrc/nslam_mc_fan.h chooses (the rule is stated with
+ * nslam_tsdf_mc_emit below, which shares it): no directed edge occurs twice and no two faces use the same
+ * three vertices, also where a face of a cell holds four crossings, and the negated volume at the negated
+ * level gives the same triangles reversed.  A value equal to the level is not below it (t is then 0 or 1 and
+ * triangles of zero area are legitimate); +-inf and NaN values are not pinned down.  A volume with a dimension
+ * of 1 holds no cell: pass 1 then flags nothing (n_verts = n_faces = 0), and pass 2 with a count above zero
+ * is NSLAM_EINVAL.  NSLAM_EUNSUPPORTED when 3 N >= 2^31. */
 int nslam_mc_count(const float* vol, int32_t nx, int32_t ny, int32_t nz, float level, void* ws, size_t ws_bytes,
                    void* stream);
 int nslam_mc_emit(const float* vol, int32_t nx, int32_t ny, int32_t nz, float level, const double* origin,
@@ -592,13 +599,15 @@ int nslam_mesh_remap(const int32_t* faces, int64_t n_faces, const int32_t* new_i
  * t = f0 / (f0 - f1) in float32, colors uint8 [n_verts][3] = floor(c + 0.5f) clamped, c = (|f1| c0 + |f0| c1) /
  * (|f0| + |f1|) in float32 (when color_pool and colors are given), and faces int32 [n_faces][3] from the loops
  * of csrc/nslam_mc_table.h with the winding flipped: right-hand normals point toward increasing TSDF, the free
- * side.  A row of that table is a fan per loop from the loop's first vertex; here every loop (l0 .. l(n-1)) is
- * fanned instead from its first vertex lk none of whose diagonals (lk, lj), j not adjacent to k, lies in a face
- * of the cell (two edges lie in a common face when they share an (axis, side) pair; every loop of every case
- * has such a vertex): triangles (lk, l(k+i), l(k+i+1)), i = 1 .. n-2, indices mod n, in the row's loop order.
- * A diagonal then belongs to two triangles of its own cell only, so no mesh edge has more than two faces, also
- * where a face of a cell holds four crossings.  Vertices are in pool / owner-edge order, faces in pool / cell
- * order.
+ * side.  A row of that table is a fan per loop from the loop's first vertex; both extractors (csrc/
+ * nslam_mc_fan.h) fan every loop (l0 .. l(n-1)) instead from a vertex lk none of whose diagonals (lk, lj), j not
+ * adjacent to k, lies in a face of the cell (two edges lie in a common face when they share an (axis, side)
+ * pair; every loop of every case has such a vertex), and of those vertices from the one with the lowest edge
+ * id: triangles (lk, l(k+i), l(k+i+1)), i = 1 .. n-2, indices mod n, in the row's loop order.  A diagonal then
+ * belongs to two triangles of its own cell only, so no mesh edge has more than two faces, also where a face of
+ * a cell holds four crossings; and the choice depends neither on where the loop's listing starts nor on its
+ * direction, so a case and its complement (the same loops, reversed) get the same triangles, reversed.
+ * Vertices are in pool / owner-edge order, faces in pool / cell order.
  * NSLAM_EINVAL (before any device call): a null pointer, n_frames outside its range, stride < 1, voxel or trunc
  * not positive, 2 trunc > 16 voxel, an empty or oversized box.  NSLAM_EUNSUPPORTED: 3 * 4096 * n_pool >= 2^31,
  * H * W >= 2^31.  No valid sample, n_list == 0, n_pool == 0 and no crossing are legal. */

@@ -11,7 +11,7 @@
 #include <math.h>
 
 #include "nslam_dev.h"
-#include "nslam_mc_table.h"
+#include "nslam_mc_fan.h"
 
 namespace {
 
@@ -226,13 +226,26 @@ __global__ __launch_bounds__(kMeshThreads) void k_mc_emit(McArgs a) {
   if (idx[0] + 1 >= a.nx || idx[1] + 1 >= a.ny || idx[2] + 1 >= a.nz) return;
   const int cs = cell_case(a, p, sx, sy);
   const int nt = kMcNumTri[cs];
+  if (nt == 0) return;
   int32_t* f = a.faces + 3 * (int64_t)a.face_off[p];
-  for (int t = 0; t < 3 * nt; ++t) {
-    const int e = kMcTri[cs][t];
-    const int ax = e >> 2, ea = e & 1, eb = (e >> 1) & 1;
-    // the lattice point that owns edge e: the offsets (a, b) fill the two other axes in ascending order
-    const int64_t q = p + (ax == 0 ? ea * sy + eb : ax == 1 ? ea * sx + eb : ea * sx + eb * sy);
-    f[t] = a.vert_off[3 * q + ax];
+  const McRow row = row_pack(cs);
+  // every loop of the row fanned from its apex (nslam_mc_fan.h), in the table's winding
+  int tr = 0;
+  while (tr < nt) {
+    uint32_t loop;
+    int n;
+    const int next = row_loop(row, nt, tr, loop, n);
+    const int apex = loop_apex(loop, n);
+    for (int i = 1; i < n - 1; ++i) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int e = fan_edge(loop, n, apex, i, k);
+        const int c = edge_owner(e);  // the lattice point that owns edge e, as a corner of this cell
+        const int64_t q = p + (c & 1) * sx + ((c >> 1) & 1) * sy + ((c >> 2) & 1);
+        f[3 * (tr + i - 1) + k] = a.vert_off[3 * q + (e >> 2)];
+      }
+    }
+    tr = next;
   }
 }
 
@@ -433,6 +446,11 @@ extern "C" int nslam_mc_count(const float* vol, int32_t nx, int32_t ny, int32_t 
   const int64_t n = (int64_t)nx * ny * nz;
   a.flags = static_cast<uint8_t*>(ws);
   a.ntri = a.flags + 3 * n;
+  if (nx < 2 || ny < 2 || nz < 2) {  // no cell: no face could use a vertex, so none is flagged
+    if (hipMemsetAsync(ws, 0, 4 * (size_t)n, reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
+      return NSLAM_EHIP - (int)hipGetLastError();
+    return NSLAM_OK;
+  }
   hipLaunchKernelGGL(k_mc_count, dim3((unsigned)blocks_for(n)), dim3(kMeshThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
   return hip_status();
@@ -446,7 +464,7 @@ extern "C" int nslam_mc_emit(const float* vol, int32_t nx, int32_t ny, int32_t n
   if (rc != NSLAM_OK) return rc;
   if (!origin || !spacing || !vert_off || !face_off || n_verts < 0 || n_faces < 0) return NSLAM_EINVAL;
   if (n_verts == 0 && n_faces == 0) return NSLAM_OK;
-  if (!verts || !faces) return NSLAM_EINVAL;
+  if (!verts || !faces || nx < 2 || ny < 2 || nz < 2) return NSLAM_EINVAL;  // a volume without a cell has no mesh
   for (int c = 0; c < 3; ++c) {
     a.origin[c] = origin[c];
     a.spacing[c] = spacing[c];

@@ -11,7 +11,7 @@
 #include <math.h>
 
 #include "nslam_dev.h"
-#include "nslam_mc_table.h"
+#include "nslam_mc_fan.h"
 
 namespace {
 
@@ -344,40 +344,6 @@ __device__ __forceinline__ bool cell_of(const McArgs& a, const Vox& v, int64_t q
   return true;
 }
 
-// edge e = axis * 4 + (a + 2 b) of a cell: the corner that owns it (the offsets (a, b) fill the two other axes
-// in ascending order)
-__device__ __forceinline__ int edge_owner(int e) {
-  const int ax = e >> 2, ea = e & 1, eb = (e >> 1) & 1;
-  return ax == 0 ? (ea << 1) | (eb << 2) : ax == 1 ? ea | (eb << 2) : ea | (eb << 1);
-}
-
-// the two faces of the cell that edge e lies in, as bits axis * 2 + side
-__device__ __forceinline__ int edge_faces(int e) {
-  const int ax = e >> 2, o1 = ax == 0 ? 1 : 0, o2 = ax == 2 ? 1 : 2;
-  return (1 << (o1 * 2 + (e & 1))) | (1 << (o2 * 2 + ((e >> 1) & 1)));
-}
-
-// A row of nslam_mc_table.h is a fan per loop, from the loop's first vertex: (l0, l1, l2), (l0, l2, l3), ...
-// With four crossings in a face of the cell that fan can put a diagonal, even a whole triangle, into the face,
-// where the neighbouring cell's fan may put the same one: an edge of four faces.  The loops are therefore
-// fanned from their first vertex whose diagonals all cross the cell's interior (every loop of every case has
-// one): a diagonal then belongs to two triangles of its own cell and to no other.  Same loops, same triangle
-// count, same winding.  A loop is held as eight 4-bit edge ids.
-__device__ __forceinline__ int loop_at(uint32_t loop, int i) { return (loop >> (4 * i)) & 15; }
-
-__device__ __forceinline__ int loop_apex(uint32_t loop, int n) {
-  for (int c = 0; c < n; ++c) {
-    bool good = true;
-    for (int d = 2; d <= n - 2; ++d) {
-      int j = c + d;
-      j -= j >= n ? n : 0;
-      good = good && (edge_faces(loop_at(loop, c)) & edge_faces(loop_at(loop, j))) == 0;
-    }
-    if (good) return c;
-  }
-  return 0;
-}
-
 __global__ __launch_bounds__(kThreads) void k_tsdf_mc_count(McArgs a) {
   const int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (p >= a.n_pool * kVox) return;
@@ -432,17 +398,12 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_mc_emit(McArgs a) {
   if (!cell_of(a, v, q, cs)) return;
   const int64_t fo = a.face_off[p];
   const int rows = min(nt, (int)kMcNumTri[cs]);
-  const signed char* T = kMcTri[cs];
+  const McRow row = row_pack(cs);
   int tr = 0;
   while (tr < rows) {
-    // the loop whose fan starts at row triangle tr
-    uint32_t loop = (uint32_t)T[3 * tr] | ((uint32_t)T[3 * tr + 1] << 4) | ((uint32_t)T[3 * tr + 2] << 8);
-    int n = 3, next = tr + 1;
-    while (next < rows && n < 8 && T[3 * next] == T[3 * tr] && T[3 * next + 1] == T[3 * next - 1]) {
-      loop |= (uint32_t)T[3 * next + 2] << (4 * n);
-      ++n;
-      ++next;
-    }
+    uint32_t loop;
+    int n;
+    const int next = row_loop(row, rows, tr, loop, n);
     const int apex = loop_apex(loop, n);
     for (int i = 1; i < n - 1; ++i) {
       const int64_t at = fo + tr + i - 1;
@@ -450,9 +411,7 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_mc_emit(McArgs a) {
       int32_t id[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        int j = apex + (k == 0 ? 0 : i + k - 1);
-        j -= j >= n ? n : 0;
-        const int e = loop_at(loop, j);
+        const int e = fan_edge(loop, n, apex, i, k);
         id[k] = a.vert_off[3 * q[edge_owner(e)] + (e >> 2)];
       }
       // the table winds toward the corners below the level; a TSDF's outside (free space) is above it

@@ -38,7 +38,11 @@ def marching_cubes(volume, level, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0
     """Indexed iso-surface of a float32 volume [nx,ny,nz] → (verts float64 [V,3], faces int32 [F,3]).
 
     One vertex per lattice edge with (a < level) != (b < level), at origin + (index + t)·spacing; vertices in
-    owner-edge order, faces in cell order, normals toward decreasing values (nslam_mc_count / nslam_mc_emit)."""
+    owner-edge order, faces in cell order, normals toward decreasing values (nslam_mc_count / nslam_mc_emit).
+    A value at the level is not below it.  Every loop of a cell is fanned from its valid apex with the lowest
+    edge id (csrc/nslam_mc_fan.h, shared with tsdf_marching_cubes): no directed edge occurs twice, also across
+    cell faces with four crossings, and the negated volume at the negated level gives every face reversed.  A
+    volume with a dimension of 1 holds no cell and gives the empty mesh (0 x 3 and 0 x 3)."""
     _want(volume, "volume", torch.float32, (None, None, None))
     nx, ny, nz = (int(v) for v in volume.shape)
     dev = volume.device

@@ -221,6 +221,7 @@ def test_marching_cubes_random_field_is_closed_and_deterministic(pkg):
     assert (np.abs(v - exp) / np.asarray(SPACING)).max() <= 1e-6
     d = _directed(f)
     key, rev = d[:, 0] * n_exp + d[:, 1], d[:, 1] * n_exp + d[:, 0]
+    assert np.unique(key).size == key.size                    # no directed edge twice (ambiguous faces included)
     assert np.array_equal(np.sort(key), np.sort(rev))         # a -> b as often as b -> a: closed
     v2, f2 = _mc(pkg, vol, 0.0)
     assert v2.tobytes() == v.tobytes() and f2.tobytes() == f.tobytes()

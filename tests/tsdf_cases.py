@@ -370,13 +370,15 @@ def row_loops(row):
 
 
 def refan(row):
-    """The row's loops fanned from their first vertex whose diagonals all cross the cell's interior (no
-    diagonal shares a face of the cell with its apex): same loops, same count, same winding."""
+    """The row's loops fanned from a vertex whose diagonals all cross the cell's interior (no diagonal shares a
+    face of the cell with its apex); of those vertices, the one with the lowest edge id, a choice that does not
+    depend on the direction in which the loop is listed: same loops, same count, same winding."""
     tris = []
     for loop in row_loops(row):
         n = len(loop)
-        apex = next(c for c in range(n)
-                    if not any(edge_faces(loop[c]) & edge_faces(loop[(c + d) % n]) for d in range(2, n - 1)))
+        apex = min((c for c in range(n)
+                    if not any(edge_faces(loop[c]) & edge_faces(loop[(c + d) % n]) for d in range(2, n - 1))),
+                   key=lambda c: loop[c])
         tris += [(loop[apex], loop[(apex + i) % n], loop[(apex + i + 1) % n]) for i in range(1, n - 1)]
     return tris
 
