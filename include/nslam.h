@@ -964,6 +964,38 @@ int nslam_sample_importance(const double* z_vals, const float* weights, const fl
                             int32_t n_samples, int32_t n_importance, double* z_out, double* z_samples,
                             void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Rendering evaluation (csrc/nslam_metrics.hip; additive, no ABI bump): the sums behind PSNR and rendered-depth
+ * L1, and SSIM / MS-SSIM.  Every workgroup writes one float64 partial per quantity into `ws` and a
+ * second launch adds the partials in index order: no float atomics, two calls give the same bits.
+ *
+ * nslam_image_errors: color, gt_color float32 [n_images][n_pix][channels] (channels 1 or 3), depth, gt_depth
+ * float32 [n_images][n_pix]; either pair may be NULL (gt_depth alone may be given as the colour mask).  out
+ * float64 [n_images][4]:
+ *   0  sum (color - gt_color)^2 over the counted colour values, color clamped to [0, 1] first when `clamp`
+ *   1  the number of counted colour values: all of them (mask_mode 0) or those of pixels with gt_depth > 0 (1)
+ *   2  sum |depth - gt_depth| over the pixels with gt_depth > 0        3  their number
+ * A missing pair leaves its two sums 0.  mask_mode 1 with colour needs gt_depth. */
+size_t nslam_image_errors_workspace_size(int32_t n_images, int64_t n_pix);
+int nslam_image_errors(const float* color, const float* gt_color, const float* depth, const float* gt_depth,
+                       int32_t n_images, int64_t n_pix, int32_t channels, int32_t mask_mode, int32_t clamp,
+                       double* out, void* ws, size_t ws_bytes, void* stream);
+
+/* nslam_ssim: x, y float32 [n_images][H][W][channels] (channels 1 or 3); out float64
+ * [n_images][levels][channels][2]: the spatial means of the SSIM map and of the CS map.
+ *   window (HOST, 11 floats): g[i] = exp(-(i-5)^2 / (2 1.5^2)) / sum, computed in float64 and rounded; it is
+ *   applied along x, then along y ("valid" correlation: the maps are (h-10) x (w-10)), in float32, taps in
+ *   ascending order, to x, y, x^2, y^2 and xy;  C1 = (0.01 L)^2, C2 = (0.03 L)^2 for L = data_range;
+ *   cs = (2 sxy + C2) / (sx + sy + C2),  ssim = (2 mx my + C1) / (mx^2 + my^2 + C1) * cs.
+ * levels is 1 or 5.  Between levels both images are averaged over 2x2 blocks with stride 2 (an odd side is first
+ * padded with one zero row / column on each side; the divisor stays 4), so a side s becomes (s + 1) / 2.
+ * levels = 1 needs min(H, W) >= 11, levels = 5 needs min(H, W) > 160; anything else is NSLAM_EINVAL.  ws holds
+ * the planar pyramid and the partials. */
+size_t nslam_ssim_workspace_size(int32_t n_images, int32_t H, int32_t W, int32_t channels, int32_t levels);
+int nslam_ssim(const float* x, const float* y, int32_t n_images, int32_t H, int32_t W, int32_t channels,
+               double data_range, const float* window, int32_t levels, double* out, void* ws, size_t ws_bytes,
+               void* stream);
+
 enum { NSLAM_WS_SAMPLER = 0 };
 size_t nslam_workspace_size(int which, int64_t n);
 

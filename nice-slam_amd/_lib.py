@@ -172,6 +172,8 @@ EXPORTS = (
     "nslam_tsdf_mc_emit",
     # depth odometry: depth maps, the volume's ray cast, ICP sums (additive: no ABI bump)
     "nslam_depth_maps", "nslam_tsdf_raycast", "nslam_icp_partials", "nslam_icp_sums",
+    # rendering evaluation: PSNR / depth-L1 sums, SSIM and MS-SSIM means (additive: no ABI bump)
+    "nslam_image_errors", "nslam_image_errors_workspace_size", "nslam_ssim", "nslam_ssim_workspace_size",
 )
 
 _lib = None
@@ -316,6 +318,12 @@ def lib():
         L.nslam_icp_partials.restype = i64
         L.nslam_icp_sums.argtypes = [vp, vp, i32, i32, i32, dp, vp, vp, i32, i32, dp, f64, f64, f64, f64, f64, f64,
                                      vp, i64, vp, vp, vp]
+        L.nslam_image_errors_workspace_size.argtypes = [i32, i64]
+        L.nslam_image_errors_workspace_size.restype = sz
+        L.nslam_image_errors.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, sz, vp]
+        L.nslam_ssim_workspace_size.argtypes = [i32, i32, i32, i32, i32]
+        L.nslam_ssim_workspace_size.restype = sz
+        L.nslam_ssim.argtypes = [vp, vp, i32, i32, i32, i32, f64, c_float_p, i32, vp, vp, sz, vp]
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L

@@ -21,8 +21,15 @@ Deviations from the reference, all stated in DESIGN.md §7b:
     restates trimesh's oriented bounds (scipy's ConvexHull, imported lazily); open3d and trimesh are absent, so
     the match with them is unpinned;
   * the trajectory plot is not built.
+
+render_metrics / eval_rendering (the reference has no such tool): PSNR, SSIM, MS-SSIM and rendered-depth
+L1 of Renderer.render_img against the frames a run was trained on, on csrc/nslam_metrics.hip (nslam_image_errors,
+nslam_ssim).  LPIPS is not computed (it needs network weights the package does not ship).
 """
 from __future__ import annotations
+
+import math
+import os
 
 import numpy as np
 import torch
@@ -712,6 +719,139 @@ def evaluate_ate_checkpoint(ckpt, scale):
     poses_gt, mask = convert_poses(ckpt["gt_c2w_list"], n, scale)
     poses_est, _ = convert_poses(ckpt["estimate_c2w_list"], n, scale, gt=False)
     return evaluate_ate(poses_gt, poses_est[mask])
+
+
+# ------------------------------------------------------------------------------------------------
+# rendering quality
+# ------------------------------------------------------------------------------------------------
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+RENDER_METRICS = ("psnr", "ssim", "ms_ssim", "depth_l1")
+
+
+def _as_image(a, device, name, dims):
+    a = torch.as_tensor(a)
+    if a.dim() != dims:
+        raise ValueError(f"render_metrics: {name} must have {dims} dimensions, got {list(a.shape)}")
+    return a.to(device=device, dtype=torch.float32).contiguous()[None]
+
+
+def _render_sums(color, gt_color, depth, gt_depth, mask, device):
+    """The device half of render_metrics → (errors float64 [4], SSIM / CS means float64 [levels,C,2]); no host
+    synchronisation.  The means have five levels when both sides exceed 160, else one."""
+    if mask not in ops.metrics.MASK_MODES:
+        raise ValueError(f"render_metrics: mask must be 'depth' or 'none', got {mask!r}")
+    if device is None:
+        device = color.device if isinstance(color, torch.Tensor) and color.is_cuda else DEVICE
+    color, gt_color = _as_image(color, device, "color", 3), _as_image(gt_color, device, "gt_color", 3)
+    depth, gt_depth = _as_image(depth, device, "depth", 2), _as_image(gt_depth, device, "gt_depth", 2)
+    errors = ops.image_errors(color, gt_color, depth, gt_depth, mask=mask, clamp=True)[0]
+    levels = ops.MS_SSIM_LEVELS if min(color.shape[1:3]) >= ops.MS_SSIM_MIN_SIDE else 1
+    means = ops.ssim(color.clamp(0.0, 1.0), gt_color, data_range=1.0, levels=levels)[0]
+    return errors, means
+
+
+def _render_values(errors, means):
+    """The host half: errors [4] and means [levels][C][2] (nested lists of floats) → the metrics dict."""
+    sq, n_color, ad, n_depth = errors
+    if n_color == 0:
+        psnr = float("nan")
+    else:
+        mse = sq / n_color
+        psnr = float("inf") if mse == 0 else -10.0 * math.log10(mse)
+    ssim = math.fsum(c[0] for c in means[0]) / len(means[0])
+    ms = None
+    if len(means) == len(MS_SSIM_WEIGHTS):
+        per_channel = []
+        for ch in range(len(means[0])):
+            v = [max(means[l][ch][1], 0.0) for l in range(len(means) - 1)] + [max(means[-1][ch][0], 0.0)]
+            per_channel.append(math.prod(x ** w for x, w in zip(v, MS_SSIM_WEIGHTS)))
+        ms = math.fsum(per_channel) / len(per_channel)
+    return {"psnr": psnr, "ssim": ssim, "ms_ssim": ms,
+            "depth_l1": ad / n_depth if n_depth > 0 else float("nan"), "valid_depth_pixels": int(n_depth)}
+
+
+def render_metrics(color, gt_color, depth, gt_depth, mask="depth", device=None):
+    """Rendering quality of one frame → {"psnr", "ssim", "ms_ssim", "depth_l1", "valid_depth_pixels"}.
+
+    color, gt_color [H,W,C] (C = 1 or 3, data range 1; the rendered colour is clamped to [0,1]), depth, gt_depth
+    [H,W]; tensors or arrays of any float type (converted to float32 on `device`).  mask "depth" counts only pixels
+    with gt_depth > 0 for the PSNR, "none" every pixel; the depth error always counts gt_depth > 0 alone.
+      psnr      -10 log10(mse); inf at mse 0, nan when no value counts
+      ssim      the mean over channels of the SSIM map's mean (11-tap Gaussian window, sigma 1.5)
+      ms_ssim   the mean over channels of the five-level product, cs and ssim clamped at 0; None when a side is
+                <= 160 (the fifth level would not hold a window)
+      depth_l1  the mean |depth - gt_depth| in the depth's own unit; nan without a valid pixel"""
+    errors, means = _render_sums(color, gt_color, depth, gt_depth, mask, device)
+    return _render_values(errors.tolist(), means.tolist())
+
+
+def last_checkpoint(output):
+    """The path of the last checkpoint under output/ckpts (eval_ate.py:283-286's rule: sorted names)."""
+    ckptsdir = os.path.join(output, "ckpts")
+    ckpts = sorted(f for f in os.listdir(ckptsdir) if "tar" in f) if os.path.isdir(ckptsdir) else []
+    if not ckpts:
+        raise FileNotFoundError(f"no checkpoint under {ckptsdir}")
+    return os.path.join(ckptsdir, ckpts[-1])
+
+
+def eval_rendering(cfg, args, ckpt_path=None, every=5, mask="depth", device=DEVICE, on_frame=None):
+    """Rendering quality of a finished run over the frames it was trained on → dict.
+
+    The run's last checkpoint (ckpt_path, else the last one under the output folder: args.output, else
+    cfg['data']['output']) gives the grids, the decoders and the estimated poses; every `every`-th frame up to
+    the checkpoint's idx is rendered at its estimated pose (Renderer.render_img, stage "color", the frame's depth
+    guiding the samples) and compared with the frame (render_metrics).  args: nice, output, input_folder, as
+    run.py's.  on_frame(idx, color, gt_color) receives the device images of every evaluated frame (the tool's
+    --save_images).  The per-frame sums stay on the device until the loop ends: one download.
+
+    Result: "frames" (indices), per-frame lists under "psnr", "ssim", "ms_ssim", "depth_l1" (a frame without a value
+    holds None), their means over the frames that have one under "mean", "frames_without_depth" and
+    "frames_without_color" (counts), "checkpoint", "every", "mask"."""
+    from . import datasets, slam
+    from .renderer import Renderer
+    every = int(every)
+    if every < 1:
+        raise ValueError("eval_rendering: every must be at least 1")
+    output = cfg["data"]["output"] if getattr(args, "output", None) is None else args.output
+    path = last_checkpoint(output) if ckpt_path is None else ckpt_path
+    ck = datasets.load_checkpoint(path, device=device)
+    nice = bool(args.nice)
+    bound = slam.load_bound(cfg)
+    decoders = slam.build_decoders(cfg, bound, device, nice=nice)
+    decoders.load_state_dict(ck["decoder_state_dict"])
+    H, W, fx, fy, cx, cy = slam.update_cam(cfg)
+    from types import SimpleNamespace
+    renderer = Renderer(cfg, args, SimpleNamespace(nice=nice, bound=bound, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy))
+    reader = datasets.get_dataset(cfg, args, cfg["scale"], device=device, color_dtype=torch.float32)
+    est = ck["estimate_c2w_list"]
+    frames = [i for i in range(0, min(int(ck["idx"]), len(reader) - 1) + 1, every)]
+    sums, means = [], []
+    for i in frames:
+        _, gt_color, gt_depth, _ = reader[i]
+        depth, _, color = renderer.render_img(ck["c"], decoders, est[i].to(device), device, stage="color",
+                                              gt_depth=gt_depth)
+        e, m = _render_sums(color, gt_color, depth, gt_depth, mask, device)
+        sums.append(e)
+        means.append(m)
+        if on_frame is not None:
+            on_frame(i, color, gt_color)
+    out = {k: [] for k in RENDER_METRICS}
+    if frames:
+        sums, means = torch.stack(sums).tolist(), torch.stack(means).tolist()  # the one download
+        for e, m in zip(sums, means):
+            v = _render_values(e, m)
+            for k in RENDER_METRICS:
+                out[k].append(None if v[k] is None or math.isnan(v[k]) else v[k])
+
+    def mean(vals):
+        have = [v for v in vals if v is not None]
+        return math.fsum(have) / len(have) if have else None
+    out["mean"] = {k: mean(out[k]) for k in RENDER_METRICS}
+    out["frames"] = frames
+    out["frames_without_depth"] = sum(v is None for v in out["depth_l1"])
+    out["frames_without_color"] = sum(v is None for v in out["psnr"])
+    out.update(checkpoint=path, every=every, mask=mask)
+    return out
 
 
 write_ply = mesher.write_ply

@@ -15,6 +15,7 @@ public name re-exported here (callers write ops.<name>).  No CPU fallback.
   raster      nslam_raster.hip     render_depth, render_scene, their workspaces, RASTER_* / SCENE_* / CULL_MODES
   imap        nslam_imap.hip       imap_params, imap_query, imap_query_rays, imap_struct, imap_query_struct
   fusion      nslam_tsdf.hip, nslam_odometry.hip (one block volume)  tsdf_*, depth_maps, icp_sums
+  metrics     nslam_metrics.hip    image_errors, ssim, ssim_window, SSIM_* / MS_SSIM_* limits
   _check      the argument checks (_want, _expect) and host conversions (bound_list) they share
 
 Two switches live here and are assigned from outside (ops.TIMER by the bench, ops.SPLIT_FWD by tests): the
@@ -115,3 +116,5 @@ from .evaluation import (NN_MAX_CELLS, NN_PER_CELL, NNGrid, depth_l1, face_areas
 from .imap import imap_params, imap_query, imap_query_rays, imap_query_struct, imap_struct  # noqa: E402,F401
 from .fusion import (depth_maps, icp_sums, tsdf_block_range, tsdf_integrate, tsdf_marching_cubes,  # noqa: E402,F401
                      tsdf_raycast, tsdf_touch)
+from .metrics import (MS_SSIM_LEVELS, MS_SSIM_MIN_SIDE, SSIM_TILE, SSIM_WIN, image_errors, ssim,  # noqa: E402,F401
+                      ssim_window)
