@@ -701,6 +701,53 @@ int nslam_icp_sums(const float* src_vertex, const float* src_normal, int32_t Hs,
                    const double* w2c, double fx, double fy, double cx, double cy, double dist_th, double cos_th,
                    double* partial, int64_t n_partial, double* out, uint8_t* mask, void* stream);
 
+/* The photometric term of the odometry (csrc/nslam_odometry.hip); additive, no ABI bump.  A source frame is
+ * aligned to a reference FRAME (not the volume): its grey level against the reference's, seen through the source's
+ * own depth.  open3d's hybrid RGB-D odometry, which the reference's own-data path relies on, is absent: parity
+ * with it is unpinned.
+ *
+ * nslam_gray_pyramid, float32, one rounding per written operation: rgb uint8 [H][W][3] -> out float32
+ * [nslam_gray_pyramid_size(H, W, levels)], the levels one after the other.  Level 0 is
+ *   g = ((0.299f R + 0.587f G) + 0.114f B) / 255.0f
+ * Level l + 1 has ceil(h / 2) x ceil(w / 2) pixels (h x w: level l); its pixel (row j, column i) is the 3 x 3
+ * binomial of level l around (2 j, 2 i) with indices clamped to the image, rows first:
+ *   hrow(y) = (0.25f L[y][2i - 1] + 0.5f L[y][2i]) + 0.25f L[y][2i + 1];  (0.25f hrow(2j - 1) + 0.5f hrow(2j)) +
+ *   0.25f hrow(2j + 1)
+ * So level l has ceil(H / 2^l) x ceil(W / 2^l) pixels and its pixel k lies at level-0 coordinate k 2^l: exactly the
+ * strided pixels nslam_icp_sums visits at stride 2^l.  One launch per level.  levels: 1 .. 8.
+ *
+ * nslam_photo_sums, float64 from float32 inputs.  src_vertex [Hs][Ws][3] (source camera frame, NaN = invalid);
+ * src_gray [src_h][src_w] and ref_gray [ref_h][ref_w]: level `level` of the two pyramids (src_h = ceil(Hs / 2^l)
+ * and so on, else NSLAM_EINVAL); ref_vertex [Hr][Wr][3]: the reference frame's own vertex map in ITS camera frame;
+ * T: source camera to world; w2c: the reference camera's world-to-camera; fx .. cy: level-0 intrinsics.  With
+ * S = 2^level, for every source pixel (u, v) = (k S, m S) whose vertex s is not NaN, in this order:
+ *   p = T s, pc = w2c p (each ((m0 x + m1 y) + m2 z) + m3 per row);  reject unless pc.z > 0
+ *   x0 = (pc.x * fx) / pc.z + cx,  y0 likewise
+ *   occlusion, at the level-0 pixel ((int)(x0 + 0.5), (int)(y0 + 0.5)): reject unless 0 <= x0 + 0.5 < Wr and
+ *   0 <= y0 + 0.5 < Hr, the reference vertex there is not NaN and fabs(pc.z - its z) <= depth_th
+ *   xl = x0 / S, yl = y0 / S, i0 = floor(xl), j0 = floor(yl): reject unless 0 <= i0, i0 + 1 <= ref_w - 1, 0 <= j0,
+ *   j0 + 1 <= ref_h - 1 (a reference level narrower or shorter than 2 pixels accepts nothing);  a = xl - i0,
+ *   b = yl - j0;  I00 = ref_gray[j0][i0], I10 = [j0][i0 + 1], I01 = [j0 + 1][i0], I11 = [j0 + 1][i0 + 1]
+ *   Iref = (1 - b) * ((1 - a) * I00 + a * I10) + b * ((1 - a) * I01 + a * I11)
+ *   gx = ((1 - b) * (I10 - I00) + b * (I11 - I01)) / S,  gy = ((1 - a) * (I01 - I00) + a * (I11 - I10)) / S: the
+ *   exact derivative of that interpolant per level-0 pixel
+ *   r = Iref - src_gray[m][k]: reject unless fabs(r) <= photo_th (1e300 = off)
+ *   z = pc.z;  gc = (gx * (fx / z), gy * (fy / z), gx * (-((fx * pc.x) / (z * z))) + gy * (-((fy * pc.y) / (z * z))))
+ *   gw = w2c's rotation transposed times gc: gw.c = (M0c * gc.x + M1c * gc.y) + M2c * gc.z
+ *   J = [p.y gw.z - p.z gw.y, p.z gw.x - p.x gw.z, p.x gw.y - p.y gw.x, gw]
+ * out float64 [29], partial, n_partial >= nslam_icp_partials(Hs, Ws, S) and mask [Hs][Ws] as for nslam_icp_sums,
+ * whose two-stage reduction this shares (the same thread, wave, workgroup and final order): two calls give the
+ * same bits.  NSLAM_EINVAL: a null pointer (mask excepted), a size < 1, level outside 0 .. 7, level image sides that
+ * do not match, fx or fy zero, an intrinsic, T or w2c that is not finite, depth_th or photo_th negative or NaN.
+ * NSLAM_EUNSUPPORTED: 3 H W >= 2^31.  NSLAM_EWORKSPACE: n_partial too small. */
+int64_t nslam_gray_pyramid_size(int32_t H, int32_t W, int32_t levels);
+int nslam_gray_pyramid(const uint8_t* rgb, int32_t H, int32_t W, int32_t levels, float* out, void* stream);
+int nslam_photo_sums(const float* src_vertex, int32_t Hs, int32_t Ws, const float* src_gray, int32_t src_h,
+                     int32_t src_w, const float* ref_gray, int32_t ref_h, int32_t ref_w, int32_t level,
+                     const float* ref_vertex, int32_t Hr, int32_t Wr, const double* T, const double* w2c, double fx,
+                     double fy, double cx, double cy, double depth_th, double photo_th, double* partial,
+                     int64_t n_partial, double* out, uint8_t* mask, void* stream);
+
 /* Evaluation (src/tools/cull_mesh.py, src/tools/eval_recon.py; csrc/nslam_eval.hip); additive, no ABI bump.
  * No entry point here uses atomics, with one exception: nslam_raster_depth (and the replay's nslam_scene_render on
  * the same passes) combines its hits with an integer atomicMin, which does not depend on the order.  Every output

@@ -172,6 +172,8 @@ EXPORTS = (
     "nslam_tsdf_mc_emit",
     # depth odometry: depth maps, the volume's ray cast, ICP sums (additive: no ABI bump)
     "nslam_depth_maps", "nslam_tsdf_raycast", "nslam_icp_partials", "nslam_icp_sums",
+    # its photometric term: grey pyramid, photometric sums (additive: no ABI bump)
+    "nslam_gray_pyramid_size", "nslam_gray_pyramid", "nslam_photo_sums",
     # rendering evaluation: PSNR / depth-L1 sums, SSIM and MS-SSIM means (additive: no ABI bump)
     "nslam_image_errors", "nslam_image_errors_workspace_size", "nslam_ssim", "nslam_ssim_workspace_size",
 )
@@ -318,6 +320,11 @@ def lib():
         L.nslam_icp_partials.restype = i64
         L.nslam_icp_sums.argtypes = [vp, vp, i32, i32, i32, dp, vp, vp, i32, i32, dp, f64, f64, f64, f64, f64, f64,
                                      vp, i64, vp, vp, vp]
+        L.nslam_gray_pyramid_size.argtypes = [i32, i32, i32]
+        L.nslam_gray_pyramid_size.restype = i64
+        L.nslam_gray_pyramid.argtypes = [vp, i32, i32, i32, vp, vp]
+        L.nslam_photo_sums.argtypes = [vp, i32, i32, vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, dp, dp, f64, f64,
+                                       f64, f64, f64, f64, vp, i64, vp, vp, vp]
         L.nslam_image_errors_workspace_size.argtypes = [i32, i64]
         L.nslam_image_errors_workspace_size.restype = sz
         L.nslam_image_errors.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, sz, vp]

@@ -3,6 +3,8 @@
 //   nslam_depth_maps     depth image -> camera-frame vertex and normal maps
 //   nslam_tsdf_raycast   the volume seen from a pose -> world-space vertex and normal maps
 //   nslam_icp_sums       projective point-to-plane association and the 29 sums of the normal equations
+//   nslam_gray_pyramid   colour image -> grey levels, each the 3 x 3 binomial of the one below at every second pixel
+//   nslam_photo_sums     the 29 sums of the photometric residual against a reference frame's grey level
 // One stream, no graph capture, no float atomics: every output is the same from run to run.  Every table,
 // pool and image index is checked before use and every loop has a fixed trip-count cap; a pose or a value
 // that is not finite ends as an invalid pixel.  The build has -ffp-contract=off: the arithmetic below rounds
@@ -280,8 +282,37 @@ __device__ __forceinline__ bool icp_term(const IcpArgs& a, int64_t i, double J[6
   return true;
 }
 
-// Each thread adds its pixels i = tid, tid + threads, ... in ascending order, a wave's 64 threads are added by
-// the xor butterfly, the workgroup's four waves in wave order, and the workgroup stores its 29 partials.
+// The reduction both sums kernels share.  Each thread adds its pixels i = tid, tid + threads, ... in ascending
+// order (add_term), a wave's 64 threads are added by the xor butterfly, the workgroup's four waves in wave order,
+// and the workgroup stores its 29 partials (store_group_sums).
+__device__ __forceinline__ void add_term(double acc[kSums], const double J[6], const double r) {
+  int j = 0;
+#pragma unroll
+  for (int x = 0; x < 6; ++x)
+#pragma unroll
+    for (int y = x; y < 6; ++y) acc[j++] += J[x] * J[y];
+#pragma unroll
+  for (int x = 0; x < 6; ++x) acc[21 + x] += J[x] * r;
+  acc[27] += r * r;
+  acc[28] += 1.0;
+}
+
+__device__ __forceinline__ void store_group_sums(const double acc[kSums], double (*lds)[kSums], double* partial) {
+  const int w = wave_id();
+#pragma unroll
+  for (int j = 0; j < kSums; ++j) {
+    const double s = wave_sum(acc[j]);
+    if ((threadIdx.x & 63) == 0) lds[w][j] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kSums) {
+    double s = lds[0][threadIdx.x];
+#pragma unroll
+    for (int k = 1; k < kThreads / 64; ++k) s += lds[k][threadIdx.x];
+    partial[(int64_t)blockIdx.x * kSums + threadIdx.x] = s;
+  }
+}
+
 __global__ __launch_bounds__(kThreads) void k_icp_partials(IcpArgs a) {
   __shared__ double lds[kThreads / 64][kSums];
   double acc[kSums];
@@ -294,29 +325,9 @@ __global__ __launch_bounds__(kThreads) void k_icp_partials(IcpArgs a) {
     const bool ok = icp_term(a, i, J, r, at);
     if (a.mask) a.mask[at] = ok ? 1 : 0;
     if (!ok) continue;
-    int j = 0;
-#pragma unroll
-    for (int x = 0; x < 6; ++x)
-#pragma unroll
-      for (int y = x; y < 6; ++y) acc[j++] += J[x] * J[y];
-#pragma unroll
-    for (int x = 0; x < 6; ++x) acc[21 + x] += J[x] * r;
-    acc[27] += r * r;
-    acc[28] += 1.0;
+    add_term(acc, J, r);
   }
-  const int w = wave_id();
-#pragma unroll
-  for (int j = 0; j < kSums; ++j) {
-    const double s = wave_sum(acc[j]);
-    if ((threadIdx.x & 63) == 0) lds[w][j] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kSums) {
-    double s = lds[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < kThreads / 64; ++k) s += lds[k][threadIdx.x];
-    a.partial[(int64_t)blockIdx.x * kSums + threadIdx.x] = s;
-  }
+  store_group_sums(acc, lds, a.partial);
 }
 
 // out[j] = the partials of workgroups 0, 1, ... added in that order.  One wave per sum j: its lanes load 64
@@ -334,6 +345,119 @@ __global__ __launch_bounds__(64) void k_icp_final(const double* partial, int32_t
     for (int i = 0; i < n; ++i) s += __shfl(v, i, 64);
   }
   if (lane == 0) out[j] = s;
+}
+
+// ------------------------------------------------------------------------------------------------
+// grey pyramid
+// ------------------------------------------------------------------------------------------------
+constexpr int kMaxLevels = 8;
+
+inline int32_t half_up(int32_t n) { return (n + 1) / 2; }
+
+__global__ __launch_bounds__(kThreads) void k_gray(const uint8_t* rgb, int64_t n, float* out) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const float r = (float)rgb[3 * i], g = (float)rgb[3 * i + 1], b = (float)rgb[3 * i + 2];
+  out[i] = ((0.299f * r + 0.587f * g) + 0.114f * b) / 255.0f;
+}
+
+// out (oh x ow) from in (h x w): pixel (i, j) is the (1/4, 1/2, 1/4) binomial around in(2 i, 2 j), rows first,
+// indices clamped to the image (2 i <= w - 1 and 2 j <= h - 1 since ow = ceil(w / 2), oh = ceil(h / 2))
+__global__ __launch_bounds__(kThreads) void k_gray_down(const float* in, int32_t h, int32_t w, float* out,
+                                                        int32_t oh, int32_t ow) {
+  const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (q >= (int64_t)oh * ow) return;
+  const int32_t i = (int32_t)(q % ow), j = (int32_t)(q / ow);
+  const int32_t x1 = 2 * i, x0 = x1 > 0 ? x1 - 1 : 0, x2 = x1 + 1 < w ? x1 + 1 : w - 1;
+  const int32_t y1 = 2 * j, y0 = y1 > 0 ? y1 - 1 : 0, y2 = y1 + 1 < h ? y1 + 1 : h - 1;
+  const float* r0 = in + (int64_t)y0 * w;
+  const float* r1 = in + (int64_t)y1 * w;
+  const float* r2 = in + (int64_t)y2 * w;
+  const float h0 = (0.25f * r0[x0] + 0.5f * r0[x1]) + 0.25f * r0[x2];
+  const float h1 = (0.25f * r1[x0] + 0.5f * r1[x1]) + 0.25f * r1[x2];
+  const float h2 = (0.25f * r2[x0] + 0.5f * r2[x1]) + 0.25f * r2[x2];
+  out[q] = (0.25f * h0 + 0.5f * h1) + 0.25f * h2;
+}
+
+// ------------------------------------------------------------------------------------------------
+// photometric sums
+// ------------------------------------------------------------------------------------------------
+struct PhotoArgs {
+  const float *sv, *sg, *rg, *rv;  // source vertices [Hs][Ws][3], source / reference grey level, reference
+                                   // vertices [Hr][Wr][3] (each in its own camera frame)
+  int32_t Hs, Ws, Hr, Wr, stride, sh, sw, rh, rw;
+  int64_t n;      // sh * sw strided source pixels = the pixels of the source level
+  double T[12];   // the estimate, rows 0..2
+  double M[12];   // the reference camera's world-to-camera, rows 0..2
+  double fx, fy, cx, cy, depth_th, photo_th, scale;  // scale = 2^level = stride
+  int32_t groups;
+  double* partial;  // [groups][29]
+  uint8_t* mask;    // [Hs][Ws] accepted pixels, or NULL
+};
+
+// the terms of strided pixel i: false when a gate rejects it
+__device__ __forceinline__ bool photo_term(const PhotoArgs& a, int64_t i, double J[6], double& r, int64_t& at) {
+  const int32_t u = (int32_t)(i % a.sw) * a.stride, v = (int32_t)(i / a.sw) * a.stride;
+  at = (int64_t)v * a.Ws + u;
+  const float* s = a.sv + 3 * at;
+  const float sx = s[0], sy = s[1], sz = s[2];
+  if (!(sx == sx && sy == sy && sz == sz)) return false;
+  double p[3], pc[3];
+  rigid(a.T, (double)sx, (double)sy, (double)sz, p);
+  rigid(a.M, p[0], p[1], p[2], pc);
+  const double z = pc[2];
+  if (!(z > 0.0)) return false;
+  const double x0 = (pc[0] * a.fx) / z + a.cx, y0 = (pc[1] * a.fy) / z + a.cy;
+  // occlusion: the reference frame's own depth at the nearest pixel
+  const double xn = x0 + 0.5, yn = y0 + 0.5;
+  if (!(xn >= 0.0 && xn < (double)a.Wr && yn >= 0.0 && yn < (double)a.Hr)) return false;
+  const int32_t un = (int32_t)xn, vn = (int32_t)yn;  // 0 <= un < Wr, 0 <= vn < Hr by the test above
+  const float* q = a.rv + 3 * ((int64_t)vn * a.Wr + un);
+  const float qx = q[0], qy = q[1], qz = q[2];
+  if (!(qx == qx && qy == qy && qz == qz)) return false;
+  if (!(fabs(z - (double)qz) <= a.depth_th)) return false;
+  // the bilinear cell of the reference level
+  const double xl = x0 / a.scale, yl = y0 / a.scale;
+  const double fi = floor(xl), fj = floor(yl);
+  if (!(fi >= 0.0 && fi + 1.0 <= (double)(a.rw - 1) && fj >= 0.0 && fj + 1.0 <= (double)(a.rh - 1))) return false;
+  const int32_t i0 = (int32_t)fi, j0 = (int32_t)fj;  // 0 <= i0 <= rw - 2, 0 <= j0 <= rh - 2 by the test above
+  const double ca = xl - fi, cb = yl - fj;
+  const float* t0 = a.rg + (int64_t)j0 * a.rw + i0;
+  const float* t1 = t0 + a.rw;
+  const double I00 = (double)t0[0], I10 = (double)t0[1], I01 = (double)t1[0], I11 = (double)t1[1];
+  const double Iref = (1.0 - cb) * ((1.0 - ca) * I00 + ca * I10) + cb * ((1.0 - ca) * I01 + ca * I11);
+  const double gx = ((1.0 - cb) * (I10 - I00) + cb * (I11 - I01)) / a.scale;
+  const double gy = ((1.0 - ca) * (I01 - I00) + ca * (I11 - I10)) / a.scale;
+  r = Iref - (double)a.sg[i];
+  if (!(fabs(r) <= a.photo_th)) return false;
+  const double zz = z * z;
+  const double gc[3] = {gx * (a.fx / z), gy * (a.fy / z),
+                        gx * (-((a.fx * pc[0]) / zz)) + gy * (-((a.fy * pc[1]) / zz))};
+  double gw[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) gw[c] = (a.M[c] * gc[0] + a.M[4 + c] * gc[1]) + a.M[8 + c] * gc[2];
+  J[0] = p[1] * gw[2] - p[2] * gw[1];
+  J[1] = p[2] * gw[0] - p[0] * gw[2];
+  J[2] = p[0] * gw[1] - p[1] * gw[0];
+  J[3] = gw[0], J[4] = gw[1], J[5] = gw[2];
+  return true;
+}
+
+__global__ __launch_bounds__(kThreads) void k_photo_partials(PhotoArgs a) {
+  __shared__ double lds[kThreads / 64][kSums];
+  double acc[kSums];
+#pragma unroll
+  for (int j = 0; j < kSums; ++j) acc[j] = 0.0;
+  const int64_t total = (int64_t)a.groups * kThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < a.n; i += total) {
+    double J[6], r;
+    int64_t at;
+    const bool ok = photo_term(a, i, J, r, at);
+    if (a.mask) a.mask[at] = ok ? 1 : 0;
+    if (!ok) continue;
+    add_term(acc, J, r);
+  }
+  store_group_sums(acc, lds, a.partial);
 }
 
 bool finite12(const double* m) {
@@ -452,6 +576,81 @@ extern "C" int nslam_icp_sums(const float* src_vertex, const float* src_normal, 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (mask && hipMemsetAsync(mask, 0, (size_t)Hs * Ws, s) != hipSuccess) return NSLAM_EHIP - (int)hipGetLastError();
   hipLaunchKernelGGL(k_icp_partials, dim3((unsigned)groups), dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL(k_icp_final, dim3(kSums), dim3(64), 0, s, (const double*)partial, (int32_t)groups, out);
+  return hip_status();
+}
+
+extern "C" int64_t nslam_gray_pyramid_size(int32_t H, int32_t W, int32_t levels) {
+  if (H <= 0 || W <= 0 || levels < 1 || levels > kMaxLevels) return 0;
+  int64_t n = 0;
+  for (int l = 0; l < levels; ++l, H = half_up(H), W = half_up(W)) n += (int64_t)H * W;
+  return n;
+}
+
+extern "C" int nslam_gray_pyramid(const uint8_t* rgb, int32_t H, int32_t W, int32_t levels, float* out,
+                                  void* stream) {
+  if (!rgb || !out || H <= 0 || W <= 0 || levels < 1 || levels > kMaxLevels) return NSLAM_EINVAL;
+  if ((int64_t)H * W >= (int64_t(1) << 31) / 3) return NSLAM_EUNSUPPORTED;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_gray, dim3((unsigned)blocks_for((int64_t)H * W)), dim3(kThreads), 0, s, rgb, (int64_t)H * W,
+                     out);
+  int32_t h = H, w = W;
+  for (int l = 1; l < levels; ++l) {
+    const int32_t oh = half_up(h), ow = half_up(w);
+    float* next = out + (int64_t)h * w;
+    hipLaunchKernelGGL(k_gray_down, dim3((unsigned)blocks_for((int64_t)oh * ow)), dim3(kThreads), 0, s,
+                       (const float*)out, h, w, next, oh, ow);
+    out = next, h = oh, w = ow;
+  }
+  return hip_status();
+}
+
+extern "C" int nslam_photo_sums(const float* src_vertex, int32_t Hs, int32_t Ws, const float* src_gray,
+                                int32_t src_h, int32_t src_w, const float* ref_gray, int32_t ref_h, int32_t ref_w,
+                                int32_t level, const float* ref_vertex, int32_t Hr, int32_t Wr, const double* T,
+                                const double* w2c, double fx, double fy, double cx, double cy, double depth_th,
+                                double photo_th, double* partial, int64_t n_partial, double* out, uint8_t* mask,
+                                void* stream) {
+  if (!src_vertex || !src_gray || !ref_gray || !ref_vertex || !T || !w2c || !out || !partial) return NSLAM_EINVAL;
+  if (Hs <= 0 || Ws <= 0 || Hr <= 0 || Wr <= 0 || level < 0 || level >= kMaxLevels) return NSLAM_EINVAL;
+  if (!(fx != 0.0) || !(fy != 0.0) || !(depth_th >= 0.0) || !(photo_th >= 0.0)) return NSLAM_EINVAL;
+  if (!(fabs(fx) <= 1.0e300 && fabs(fy) <= 1.0e300 && fabs(cx) <= 1.0e300 && fabs(cy) <= 1.0e300)) return NSLAM_EINVAL;
+  if (!finite12(T) || !finite12(w2c)) return NSLAM_EINVAL;
+  if ((int64_t)Hs * Ws >= (int64_t(1) << 31) / 3 || (int64_t)Hr * Wr >= (int64_t(1) << 31) / 3)
+    return NSLAM_EUNSUPPORTED;
+  const int32_t stride = 1 << level;
+  PhotoArgs a{};
+  a.sh = (Hs + stride - 1) / stride;
+  a.sw = (Ws + stride - 1) / stride;
+  a.rh = (Hr + stride - 1) / stride;
+  a.rw = (Wr + stride - 1) / stride;
+  if (src_h != a.sh || src_w != a.sw || ref_h != a.rh || ref_w != a.rw) return NSLAM_EINVAL;
+  const int64_t groups = nslam_icp_partials(Hs, Ws, stride);
+  if (n_partial < groups) return NSLAM_EWORKSPACE;
+  a.sv = src_vertex;
+  a.sg = src_gray;
+  a.rg = ref_gray;
+  a.rv = ref_vertex;
+  a.Hs = Hs;
+  a.Ws = Ws;
+  a.Hr = Hr;
+  a.Wr = Wr;
+  a.stride = stride;
+  a.n = (int64_t)a.sh * a.sw;
+  for (int k = 0; k < 12; ++k) a.T[k] = T[k], a.M[k] = w2c[k];
+  a.fx = fx;
+  a.fy = fy;
+  a.cx = cx;
+  a.cy = cy;
+  a.depth_th = depth_th;
+  a.photo_th = photo_th;
+  a.scale = (double)stride;
+  a.groups = (int32_t)groups;
+  a.partial = partial;
+  a.mask = mask;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (mask && hipMemsetAsync(mask, 0, (size_t)Hs * Ws, s) != hipSuccess) return NSLAM_EHIP - (int)hipGetLastError();
+  hipLaunchKernelGGL(k_photo_partials, dim3((unsigned)groups), dim3(kThreads), 0, s, a);
   hipLaunchKernelGGL(k_icp_final, dim3(kSums), dim3(64), 0, s, (const double*)partial, (int32_t)groups, out);
   return hip_status();
 }

@@ -5,7 +5,9 @@ KinectFusion's loop: the volume is ray cast from the last pose into a world-spac
 depth frame is aligned to that map by projective point-to-plane ICP, and the aligned frame is fused.  It stands in
 for the open3d reconstruction system the reference's own-data path needs (scene/trajectory.log and
 scene/integrated.ply for src/tools/prep_own_data.py); open3d is not a dependency, and parity with its odometry is
-unpinned.  Poses are camera-to-world matrices in the volume's convention (+z forward, y down),
+unpinned.  With photo_weight > 0 the alignment also compares the colour images (a photometric term
+against the last tracked frame), which holds a pose that sees one textured plane only.  Poses are
+camera-to-world matrices in the volume's convention (+z forward, y down),
 relative to the first camera.
 """
 from __future__ import annotations
@@ -78,6 +80,14 @@ def icp_step(sums, min_inliers, max_cond):
     return np.linalg.solve(A, -b), n, rms, cond
 
 
+def combine_sums(geo, photo, photo_weight):
+    """The 29 sums of one hybrid iteration: entries 0 to 27 are geo + photo_weight * photo, entry 28 stays the
+    geometric inlier count."""
+    out = np.array(geo, dtype=np.float64, copy=True)
+    out[:28] = out[:28] + photo_weight * np.asarray(photo, dtype=np.float64)[:28]
+    return out
+
+
 def predict(poses):
     """The constant-velocity prediction of the next pose from a list of poses (the last one repeated twice over)."""
     if len(poses) < 2:
@@ -96,19 +106,45 @@ def write_trajectory_log(path, poses):
                 f.write(" ".join(repr(float(x)) for x in m[r]) + "\n")
 
 
+PHOTO_OFF = 1.0e300     # a photo_th that gates nothing
+
+# The default weight of the photometric term in tools/prep_own_data.py --photometric: grey residuals are in units
+# of [0, 1] per pixel against metres of the point-to-plane term.  Tuned on the synthetic 48 x 64 scenes of
+# tests/rgbd_cases.py only (DESIGN.md §7k holds the sweep); no real sequence has been run.
+PHOTO_WEIGHT = 1.0
+
+
 class DepthOdometry(object):
 
     def __init__(self, H, W, fx, fy, cx, cy, voxel_length, sdf_trunc, extent, device, depth_trunc, max_jump,
                  dist_th=0.1, angle_deg=30, strides=(4, 2, 1), iters=(4, 5, 10), fuse_every=1, color=False,
-                 min_inliers=50, max_cond=1.0e4, near=0.1, depth_stride=4):
+                 min_inliers=50, max_cond=1.0e4, near=0.1, depth_stride=4, photo_weight=0.0, photo_th=None,
+                 photo_depth_th=None):
         """An H x W pinhole camera tracked through a volume of voxel_length / sdf_trunc whose block box is the
         cube of half-edge `extent` around the first camera, fixed for the whole run.  depth_trunc, max_jump: the
         depth validity and the normal maps' discontinuity threshold; dist_th, angle_deg: the association gates;
         strides / iters: the ICP schedule, coarse to fine; a frame is fused when its index is a multiple of
         fuse_every; a frame is lost when an iteration has fewer than min_inliers inliers or a normal matrix whose
-        condition number exceeds max_cond; the ray cast starts `near` in front of the camera."""
+        condition number exceeds max_cond; the ray cast starts `near` in front of the camera.
+
+        photo_weight > 0 adds the photometric term (ops.photo_sums) against the last frame that was not lost: the
+        sums of every iteration are geometric + photo_weight * photometric, at the pyramid level log2(stride), so
+        every stride must be a power of two and track needs the colour image.  photo_th: the residual gate in grey
+        units of [0, 1] (None: off); photo_depth_th: the occlusion gate (None: dist_th).  With photo_weight = 0
+        (the default) nothing of this runs."""
         if len(strides) != len(iters) or not strides:
             raise ValueError("strides and iters: one iteration count per stride expected")
+        self.photo_weight = float(photo_weight)
+        if not self.photo_weight >= 0.0 or not math.isfinite(self.photo_weight):
+            raise ValueError("photo_weight must be finite and not negative")
+        if self.photo_weight > 0 and any(int(s) < 1 or int(s) > 128 or int(s) & (int(s) - 1) for s in strides):
+            raise ValueError("photo_weight > 0: every stride must be a power of two (at most 128)")
+        self.photo_th = PHOTO_OFF if photo_th is None else float(photo_th)
+        self.photo_depth_th = float(dist_th if photo_depth_th is None else photo_depth_th)
+        if not self.photo_th >= 0.0 or not self.photo_depth_th >= 0.0:
+            raise ValueError("photo_th and photo_depth_th must not be negative")
+        self._ref = None      # the photometric reference: (grey pyramid, vertex map, pose) of the last tracked frame
+        self._src = None      # the same of the frame being tracked
         if not float(extent) > 0:
             raise ValueError("extent must be positive")
         self.H, self.W = int(H), int(W)
@@ -142,9 +178,11 @@ class DepthOdometry(object):
                              f"volume: extent = {self.extent} around the first camera is too small")
         self.fused.append(len(self.poses))
 
-    def align(self, depth, T):
+    def align(self, depth, T, gray=None):
         """ICP of a depth frame against the ray cast from the last pose, from the estimate T →
-        (T, inliers, rms, lost).  One 29-double download per iteration."""
+        (T, inliers, rms, lost).  One 29-double download per iteration.  With `gray` (the frame's grey pyramid) and
+        a photometric reference, every iteration adds photo_weight times the photometric sums against that
+        reference (a second download) and self.photo holds (photo_inliers, photo_rms) of the final pose."""
         sv, sn = ops.depth_maps(depth, self.fx, self.fy, self.cx, self.cy, self.depth_trunc, self.max_jump)
         last = self.poses[-1]
         mv, mn = self.volume.raycast(last, self.H, self.W, self.fx, self.fy, self.cx, self.cy, self.near, self.far)
@@ -154,19 +192,47 @@ class DepthOdometry(object):
             return ops.icp_sums(sv, sn, T, mv, mn, w2c, self.fx, self.fy, self.cx, self.cy, stride, self.dist_th,
                                 self.cos_th).cpu().numpy()
 
+        if gray is None:
+            T = T.copy()
+            for stride, n_it in zip(self.strides, self.iters):
+                for _ in range(n_it):
+                    xi, n, rms, _ = icp_step(sums(T, stride), self.min_inliers, self.max_cond)
+                    if xi is None:
+                        return T, n, rms, True
+                    T = se3_exp(xi) @ T
+            _, _, rr, n = normal_equations(sums(T, self.strides[-1]))
+            return T, n, (math.sqrt(rr / n) if n > 0 else float("inf")), n < self.min_inliers
+
+        self._src = (gray, sv)      # frame 0 is never lost: from frame 1 on there is a reference
+        ref_gray, ref_vertex, ref_pose = self._ref
+        ref_w2c = np.linalg.inv(ref_pose)
+
+        def photo(T, stride):
+            level = stride.bit_length() - 1
+            return ops.photo_sums(sv, gray[level], ref_gray[level], level, ref_vertex, T, ref_w2c, self.fx, self.fy,
+                                  self.cx, self.cy, self.photo_depth_th, self.photo_th).cpu().numpy()
+
+        def rms_of(s):
+            return math.sqrt(s[27] / s[28]) if s[28] > 0 else float("inf")
+
         T = T.copy()
         for stride, n_it in zip(self.strides, self.iters):
             for _ in range(n_it):
-                xi, n, rms, _ = icp_step(sums(T, stride), self.min_inliers, self.max_cond)
+                geo, pho = sums(T, stride), photo(T, stride)
+                xi, n, _, _ = icp_step(combine_sums(geo, pho, self.photo_weight), self.min_inliers, self.max_cond)
                 if xi is None:
-                    return T, n, rms, True
+                    self.photo = (int(round(float(pho[28]))), rms_of(pho))
+                    return T, n, rms_of(geo), True
                 T = se3_exp(xi) @ T
-        _, _, rr, n = normal_equations(sums(T, self.strides[-1]))
-        return T, n, (math.sqrt(rr / n) if n > 0 else float("inf")), n < self.min_inliers
+        geo, pho = sums(T, self.strides[-1]), photo(T, self.strides[-1])
+        self.photo = (int(round(float(pho[28]))), rms_of(pho))
+        n = int(round(float(geo[28])))
+        return T, n, rms_of(geo), n < self.min_inliers
 
     def track(self, depth, color=None):
-        """Track one frame → dict(c2w float64 [4,4], inliers, rms, lost).  depth: float32 [H,W] (tensor or
-        array, moved to the device); color: uint8 [H,W,3] for a volume with colour.
+        """Track one frame → dict(c2w float64 [4,4], inliers, rms, lost; with photo_weight > 0 also photo_inliers,
+        photo_rms, while inliers and rms stay the geometric ones).  depth: float32 [H,W] (tensor or array, moved to
+        the device); color: uint8 [H,W,3] for a volume with colour or a photometric term.
 
         Frame 0 gets the identity.  Later frames start from the constant-velocity prediction and run ICP against
         the ray cast from the last pose; every iteration downloads its 29 sums and solves the 6x6 system on the
@@ -179,16 +245,33 @@ class DepthOdometry(object):
             raise ValueError(f"depth: [{self.H},{self.W}] expected")
         if color is not None and not isinstance(color, torch.Tensor):
             color = torch.from_numpy(np.ascontiguousarray(color, dtype=np.uint8))
+        gray = None
+        if self.photo_weight > 0:
+            if color is None:
+                raise ValueError("an odometry with a photometric term needs a colour image per frame")
+            rgb = color.to(self.device).contiguous()
+            if tuple(rgb.shape) != (self.H, self.W, 3) or rgb.dtype != torch.uint8:
+                raise ValueError(f"color: uint8 [{self.H},{self.W},3] expected")
+            gray = ops.gray_pyramid(rgb, max(self.strides).bit_length())
         index = len(self.poses)
+        self.photo = (0, 0.0)
         if index == 0:
             c2w, inliers, rms, lost = np.eye(4), 0, 0.0, False
+            if gray is not None:
+                self._src = (gray, ops.depth_maps(depth, self.fx, self.fy, self.cx, self.cy, self.depth_trunc,
+                                                  self.max_jump)[0])
         else:
             pred = predict(self.poses)
-            c2w, inliers, rms, lost = self.align(depth, pred)
+            c2w, inliers, rms, lost = self.align(depth, pred, gray)
             if lost:
                 c2w = pred
                 self.lost.append(index)
         if not lost and index % self.fuse_every == 0:
             self._fuse(depth, color, c2w)
+        if gray is not None and not lost:       # the tracked frame's buffers become the reference
+            self._ref, self._src = (self._src[0], self._src[1], c2w.copy()), None
         self.poses.append(c2w)
-        return {"c2w": c2w.copy(), "inliers": inliers, "rms": rms, "lost": lost}
+        out = {"c2w": c2w.copy(), "inliers": inliers, "rms": rms, "lost": lost}
+        if gray is not None:
+            out["photo_inliers"], out["photo_rms"] = self.photo
+        return out

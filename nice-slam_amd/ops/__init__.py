@@ -14,7 +14,8 @@ public name re-exported here (callers write ops.<name>).  No CPU fallback.
                                    nn_cell_grid, transform_points, kabsch_sums
   raster      nslam_raster.hip     render_depth, render_scene, their workspaces, RASTER_* / SCENE_* / CULL_MODES
   imap        nslam_imap.hip       imap_params, imap_query, imap_query_rays, imap_struct, imap_query_struct
-  fusion      nslam_tsdf.hip, nslam_odometry.hip (one block volume)  tsdf_*, depth_maps, icp_sums
+  fusion      nslam_tsdf.hip, nslam_odometry.hip (one block volume)  tsdf_*, depth_maps, icp_sums,
+                                   gray_pyramid, photo_sums
   metrics     nslam_metrics.hip    image_errors, ssim, ssim_window, SSIM_* / MS_SSIM_* limits
   _check      the argument checks (_want, _expect) and host conversions (bound_list) they share
 
@@ -114,7 +115,7 @@ from .raster import (CULL_MODES, RASTER_ALL, RASTER_BIG, RASTER_CLEAR, RASTER_MA
 from .evaluation import (NN_MAX_CELLS, NN_PER_CELL, NNGrid, depth_l1, face_areas, frustum_seen,  # noqa: E402,F401
                          kabsch_sums, nn_cell_grid, sample_surface, transform_points, views_see_any)
 from .imap import imap_params, imap_query, imap_query_rays, imap_query_struct, imap_struct  # noqa: E402,F401
-from .fusion import (depth_maps, icp_sums, tsdf_block_range, tsdf_integrate, tsdf_marching_cubes,  # noqa: E402,F401
-                     tsdf_raycast, tsdf_touch)
+from .fusion import (depth_maps, gray_pyramid, icp_sums, photo_sums, tsdf_block_range,  # noqa: E402,F401
+                     tsdf_integrate, tsdf_marching_cubes, tsdf_raycast, tsdf_touch)
 from .metrics import (MS_SSIM_LEVELS, MS_SSIM_MIN_SIDE, SSIM_TILE, SSIM_WIN, image_errors, ssim,  # noqa: E402,F401
                       ssim_window)

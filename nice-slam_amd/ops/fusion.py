@@ -166,3 +166,61 @@ def icp_sums(src_vertex, src_normal, T, model_vertex, model_normal, w2c, fx, fy,
                               ptr(mask), stream_ptr(dev))
     check(rc, "nslam_icp_sums")
     return (out, mask) if return_mask else out
+
+
+def gray_pyramid(rgb, levels):
+    """nslam_gray_pyramid → a list of `levels` float32 [h_l, w_l] views of one buffer, h_l = ceil(H / 2^l): level 0
+    is the grey image in [0, 1], every further level the 3 x 3 binomial of the one below at every second pixel.
+
+    rgb uint8 [H,W,3]; levels 1 to 8."""
+    _want(rgb, "rgb", torch.uint8, (None, None, 3))
+    H, W, levels = int(rgb.shape[0]), int(rgb.shape[1]), int(levels)
+    if H < 1 or W < 1:
+        raise ValueError("gray_pyramid: an empty image")
+    if not 1 <= levels <= 8:
+        raise ValueError("gray_pyramid: 1 to 8 levels expected")
+    dev = rgb.device
+    out = torch.empty(int(lib().nslam_gray_pyramid_size(H, W, levels)), dtype=torch.float32, device=dev)
+    rc = lib().nslam_gray_pyramid(ptr(rgb), H, W, levels, ptr(out), stream_ptr(dev))
+    check(rc, "nslam_gray_pyramid")
+    views, at, h, w = [], 0, H, W
+    for _ in range(levels):
+        views.append(out[at:at + h * w].view(h, w))
+        at, h, w = at + h * w, (h + 1) // 2, (w + 1) // 2
+    return views
+
+
+def photo_sums(src_vertex, src_gray, ref_gray, level, ref_vertex, T, w2c, fx, fy, cx, cy, depth_th, photo_th,
+               return_mask=False):
+    """nslam_photo_sums → float64 [29] on the device, laid out as icp_sums': the upper triangle of sum J J^T (21),
+    sum J r (6), sum r^2 and the count of the photometric residual r = I_ref(projection) - I_src (with return_mask
+    also uint8 [Hs,Ws]: the accepted source pixels).
+
+    src_vertex float32 [Hs,Ws,3] (source camera frame); src_gray / ref_gray: level `level` of the two frames'
+    gray_pyramid, float32 [ceil(Hs / 2^level), ceil(Ws / 2^level)] and likewise for the reference; ref_vertex
+    float32 [Hr,Wr,3]: the reference frame's own vertex map in its camera frame; T (source camera to world) and
+    w2c (of the reference camera): 4x4 poses read on the host."""
+    level = int(level)
+    if not 0 <= level <= 7:
+        raise ValueError("photo_sums: level 0 to 7 expected")
+    _want(src_vertex, "src_vertex", torch.float32, (None, None, 3))
+    Hs, Ws = int(src_vertex.shape[0]), int(src_vertex.shape[1])
+    _want(ref_vertex, "ref_vertex", torch.float32, (None, None, 3))
+    Hr, Wr = int(ref_vertex.shape[0]), int(ref_vertex.shape[1])
+    if min(Hs, Ws, Hr, Wr) < 1:
+        raise ValueError("photo_sums: non-empty maps expected")
+    S = 1 << level
+    sh, sw, rh, rw = -(-Hs // S), -(-Ws // S), -(-Hr // S), -(-Wr // S)
+    _want(src_gray, "src_gray", torch.float32, (sh, sw))
+    _want(ref_gray, "ref_gray", torch.float32, (rh, rw))
+    dev = src_vertex.device
+    groups = int(lib().nslam_icp_partials(Hs, Ws, S))
+    partial = torch.empty(groups, 29, dtype=torch.float64, device=dev)
+    out = torch.empty(29, dtype=torch.float64, device=dev)
+    mask = torch.empty(Hs, Ws, dtype=torch.uint8, device=dev) if return_mask else None
+    rc = lib().nslam_photo_sums(ptr(src_vertex), Hs, Ws, ptr(src_gray), sh, sw, ptr(ref_gray), rh, rw, level,
+                                ptr(ref_vertex), Hr, Wr, _pose16(T, "T"), _pose16(w2c, "w2c"), float(fx), float(fy),
+                                float(cx), float(cy), float(depth_th), float(photo_th), ptr(partial), groups,
+                                ptr(out), ptr(mask), stream_ptr(dev))
+    check(rc, "nslam_photo_sums")
+    return (out, mask) if return_mask else out

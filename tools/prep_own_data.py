@@ -3,6 +3,7 @@
 
     python tools/prep_own_data.py --scene_folder DIR --output_config FILE [--base configs/Own/own.yaml]
                                   [--voxel L] [--trunc T] [--extent E] [--fuse_every N] [--depth_trunc D] [--force]
+                                  [--photometric [--photo_weight W] [--photo_th G]]
 
 DIR holds color/*.jpg, depth/*.png (16-bit, millimetres unless the base config says otherwise) and intrinsic.json,
 as the Azure Kinect recorder writes them.  When DIR/scene/integrated.ply exists it is used as it is: no odometry,
@@ -11,6 +12,12 @@ of a TSDF volume and point-to-plane ICP), every N-th frame (default 5) is fused 
 writes DIR/scene/trajectory.log (5 lines per frame: a header, then the +z-forward camera-to-world matrix, the
 format datasets.Azure reads) and DIR/scene/integrated.ply.  Neither file is overwritten without --force.  If the
 odometry lost a frame the tool names the frames and exits with status 2 after writing its files.
+
+Depth alone cannot hold a pose that sees one plane only (a wall, a floor, a table top): such frames are lost.
+--photometric adds the colour images to the alignment (a photometric term against the last tracked frame, weighted
+by --photo_weight, default odometry.PHOTO_WEIGHT), which holds the pose wherever the plane has texture; --photo_th
+leaves out pixels whose grey values (0 to 1) differ by more than G, e.g. 0.1 against blank or badly exposed frames
+(default: no gate).  The default weight was tuned on synthetic 48 x 64 images only.
 
 FILE gets what the reference writes: inherit_from, cam (H, W, fx, fy, cx, cy from intrinsic.json), data.input_folder,
 data.output, and mapping.bound / mapping.marching_cubes_bound = the mesh's axis-aligned box grown by 1.0 per side
@@ -59,9 +66,13 @@ def track_and_fuse(a, cam):
     if not depths or len(colors) != len(depths):
         raise SystemExit(f"prep_own_data: {len(colors)} colour and {len(depths)} depth images under {a.scene_folder}")
     scale = np.float32(depth_scale(a.base))
+    photo = {}
+    if a.photometric:
+        photo["photo_weight"] = P.odometry.PHOTO_WEIGHT if a.photo_weight is None else a.photo_weight
+        photo["photo_th"] = a.photo_th
     od = P.odometry.DepthOdometry(cam["H"], cam["W"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], a.voxel, a.trunc,
                                   a.extent, "cuda:0", a.depth_trunc, max_jump=a.trunc, fuse_every=a.fuse_every,
-                                  color=True)
+                                  color=True, **photo)
     poses, lost = [], []
     for i, (cp, dp) in enumerate(zip(colors, depths)):
         depth = P.datasets._read_depth(dp).astype(np.float32) / scale
@@ -105,7 +116,14 @@ def main(argv=None):
     ap.add_argument("--fuse_every", type=int, default=5, help="fuse every N-th frame")
     ap.add_argument("--depth_trunc", type=float, default=5.0, help="depths beyond this are ignored")
     ap.add_argument("--force", action="store_true", help="overwrite scene/trajectory.log and scene/integrated.ply")
+    ap.add_argument("--photometric", action="store_true", help="align the colour images too (textured planes)")
+    ap.add_argument("--photo_weight", type=float, default=None, help="weight of the photometric term")
+    ap.add_argument("--photo_th", type=float, default=None, help="grey residual gate of the photometric term")
     a = ap.parse_args(argv)
+    if a.photo_weight is not None and not (a.photometric and a.photo_weight > 0):
+        raise SystemExit("prep_own_data: --photo_weight needs --photometric and a positive weight")
+    if a.photo_th is not None and not (a.photometric and a.photo_th >= 0):
+        raise SystemExit("prep_own_data: --photo_th needs --photometric and must not be negative")
     if a.fuse_every < 1:
         raise SystemExit("prep_own_data: --fuse_every must be at least 1")
     cam = read_intrinsic(a.scene_folder)
