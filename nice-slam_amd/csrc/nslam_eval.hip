@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "nslam_dev.h"
+#include "nslam_reduce.h"
 
 namespace {
 
@@ -85,21 +86,15 @@ __global__ __launch_bounds__(kEvalThreads) void k_views_see_any(SeenArgs a) {
   if (__ballot(hit) != 0 && (threadIdx.x & 63) == 0) a.seen[view] = 1;
 }
 
-// out[view] = mean |a - b| over the view's n_pix pixels in float64: every thread adds its pixels in order, then
-// __shfl_down over the wave, then the waves in order through LDS (k_kabsch_sums' pattern) — the same sum every run
+// out[view] = mean |a - b| over the view's n_pix pixels in float64: every thread adds its pixels in order, the
+// workgroup's sum is nslam_reduce.h's — the same sum every run
 __global__ __launch_bounds__(kEvalThreads) void k_depth_l1(const float* a, const float* b, int64_t n_pix, double* out) {
-  __shared__ double part[kEvalThreads / 64];
+  __shared__ double part[kEvalThreads / 64][1];
   const gptr_t<float> ga = as_global(a) + (int64_t)blockIdx.x * n_pix, gb = as_global(b) + (int64_t)blockIdx.x * n_pix;
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n_pix; i += kEvalThreads) s += fabs((double)ga[i] - (double)gb[i]);
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = part[0];
-    for (int w = 1; w < kEvalThreads / 64; ++w) t += part[w];
-    out[blockIdx.x] = t / (double)n_pix;
-  }
+  double s[1] = {0.0};
+  for (int64_t i = threadIdx.x; i < n_pix; i += kEvalThreads) s[0] += fabs((double)ga[i] - (double)gb[i]);
+  const double t = group_sum<kEvalThreads>(s, part);
+  if (threadIdx.x == 0) out[blockIdx.x] = t / (double)n_pix;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -278,7 +273,7 @@ __global__ __launch_bounds__(kEvalThreads) void k_transform(const double* pts, i
 }
 
 // partials[wg][17] over the workgroup's kKabschItems * 256 points with idx >= 0: every thread adds its points
-// in order, then __shfl_down over the wave, then the waves in order through LDS — the same sum every run
+// in order, the workgroup's sums are nslam_reduce.h's — the same sums every run
 __global__ __launch_bounds__(kEvalThreads) void k_kabsch_sums(const double* src, const int32_t* idx, int64_t n,
                                                               const double* targets, int64_t m,
                                                               double* partials) {
@@ -308,20 +303,8 @@ __global__ __launch_bounds__(kEvalThreads) void k_kabsch_sums(const double* src,
     }
     s[16] += e2;
   }
-#pragma unroll
-  for (int v = 0; v < kKabschVals; ++v)
-    for (int off = 32; off > 0; off >>= 1) s[v] += __shfl_down(s[v], off, 64);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int v = 0; v < kKabschVals; ++v) part[wave][v] = s[v];
-  }
-  __syncthreads();
-  if (threadIdx.x < kKabschVals) {
-    double t = part[0][threadIdx.x];
-    for (int w = 1; w < kEvalThreads / 64; ++w) t += part[w][threadIdx.x];
-    partials[(int64_t)blockIdx.x * kKabschVals + threadIdx.x] = t;
-  }
+  const double t = group_sum<kEvalThreads>(s, part);
+  if (threadIdx.x < kKabschVals) partials[(int64_t)blockIdx.x * kKabschVals + threadIdx.x] = t;
 }
 
 inline bool finite_d(double v) { return v == v && v - v == 0.0; }

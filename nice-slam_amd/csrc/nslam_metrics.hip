@@ -4,62 +4,19 @@
 //                        Wang, Simoncelli, Bovik 2003 for the five-level form): 11-tap Gaussian window, "valid"
 //                        correlation, 2x2 mean pooling between levels
 // Sums: every workgroup writes ONE float64 partial per quantity to the workspace and a second launch adds the
-// partials in index order — no float atomics and no tickets, so two calls give the same bits.
+// partials in index order, so two calls give the same bits (nslam_reduce.h has the order and the two sums).
 // Float32 order of the SSIM maps (the build has -ffp-contract=off; tests/metrics_cases.py restates it): products
 // x², y², xy first, then per moment the horizontal pass Σ_i g[i]·v[c+i] with i ascending from a zero sum, then the
 // vertical pass over the horizontal results in the same way, then the formulas of ssim_point() as written.
 #include <math.h>
 
 #include "nslam_dev.h"
+#include "nslam_reduce.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-
-// the waves' values in wave order through LDS; the result is valid in thread 0 (K values per thread)
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*part)[K]) {
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) part[threadIdx.x >> 6][k] = v[k];
-  __syncthreads();
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      double t = part[0][k];
-      for (int w = 1; w < kWaves; ++w) t += part[w][k];
-      v[k] = t;
-    }
-}
-
-// lane i's value of v as a wave-uniform value (i: a constant once the caller's loop is unrolled): two v_readlane
-__device__ __forceinline__ double lane_value(double v, int i) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, i);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), i);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
-// Σ_j p[j·stride], j ascending, by one wave (after nslam_odometry.hip's k_icp_final): its lanes load 64 consecutive
-// partials at once, then the 64 values are added in lane order, so the additions are the serial ones while the
-// loads take n / 64 rounds, not n.  Lanes past n hold +0, which leaves the sum's value as it is.  The values come
-// through v_readlane, not a shuffle: the chain is 64 dependent v_add_f64, with no LDS round trip inside it (with
-// __shfl the 798 partials of a 680 x 1200 level took 41 us, most of it that latency).
-__device__ __forceinline__ double wave_ordered_sum(gptr_t<double> p, int32_t n, int64_t stride) {
-  const int lane = threadIdx.x & 63;
-  double s = 0.0;
-  for (int32_t base = 0; base < n; base += 64) {  // uniform
-    const int32_t j = base + lane;
-    const double v = j < n ? p[(int64_t)j * stride] : 0.0;
-#pragma unroll
-    for (int i = 0; i < 64; ++i) s += lane_value(v, i);
-  }
-  return s;
-}
 
 // ------------------------------------------------------------------------------------------------
 // image errors
@@ -112,11 +69,8 @@ __global__ __launch_bounds__(kThreads) void k_image_errors(ErrArgs a) {
       }
     }
   }
-  block_sum<4>(s, part);
-  if (threadIdx.x == 0) {
-    double* o = a.partials + (img * a.blocks + blockIdx.x) * 4;
-    for (int k = 0; k < 4; ++k) o[k] = s[k];
-  }
+  const double t = group_sum<kThreads>(s, part);
+  if (threadIdx.x < 4) a.partials[(img * a.blocks + blockIdx.x) * 4 + threadIdx.x] = t;
 }
 
 // out[i][k] = Σ_j partials[i][j][k], j ascending: one wave per output value, grid n_out · K
@@ -235,12 +189,8 @@ __global__ __launch_bounds__(kThreads) void k_ssim_level(SsimArgs a) {
       s[1] += (double)cs;
     }
   }
-  block_sum<2>(s, part);
-  if (tid == 0) {
-    double* o = a.partials + (((int64_t)plane * a.tiles_y + blockIdx.y) * a.tiles_x + blockIdx.x) * 2;
-    o[0] = s[0];
-    o[1] = s[1];
-  }
+  const double t = group_sum<kThreads>(s, part);
+  if (tid < 2) a.partials[(((int64_t)plane * a.tiles_y + blockIdx.y) * a.tiles_x + blockIdx.x) * 2 + tid] = t;
 }
 
 struct PoolArgs {

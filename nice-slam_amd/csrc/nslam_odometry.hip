@@ -5,13 +5,14 @@
 //   nslam_icp_sums       projective point-to-plane association and the 29 sums of the normal equations
 //   nslam_gray_pyramid   colour image -> grey levels, each the 3 x 3 binomial of the one below at every second pixel
 //   nslam_photo_sums     the 29 sums of the photometric residual against a reference frame's grey level
-// One stream, no graph capture, no float atomics: every output is the same from run to run.  Every table,
-// pool and image index is checked before use and every loop has a fixed trip-count cap; a pose or a value
-// that is not finite ends as an invalid pixel.  The build has -ffp-contract=off: the arithmetic below rounds
-// where include/nslam.h says it does.
+// One stream, no graph capture, no float atomics: every output is the same from run to run (the 29 sums are
+// added in nslam_reduce.h's order).  Every table, pool and image index is checked before use and every loop has
+// a fixed trip-count cap; a pose or a value that is not finite ends as an invalid pixel.  The build has
+// -ffp-contract=off: the arithmetic below rounds where include/nslam.h says it does.
 #include <math.h>
 
 #include "nslam_dev.h"
+#include "nslam_reduce.h"
 
 namespace {
 
@@ -283,8 +284,8 @@ __device__ __forceinline__ bool icp_term(const IcpArgs& a, int64_t i, double J[6
 }
 
 // The reduction both sums kernels share.  Each thread adds its pixels i = tid, tid + threads, ... in ascending
-// order (add_term), a wave's 64 threads are added by the xor butterfly, the workgroup's four waves in wave order,
-// and the workgroup stores its 29 partials (store_group_sums).
+// order (add_term); the workgroup's 29 partials are nslam_reduce.h's group_sum (store_group_sums), and k_icp_final
+// adds the workgroups' partials with its wave_ordered_sum.
 __device__ __forceinline__ void add_term(double acc[kSums], const double J[6], const double r) {
   int j = 0;
 #pragma unroll
@@ -297,20 +298,9 @@ __device__ __forceinline__ void add_term(double acc[kSums], const double J[6], c
   acc[28] += 1.0;
 }
 
-__device__ __forceinline__ void store_group_sums(const double acc[kSums], double (*lds)[kSums], double* partial) {
-  const int w = wave_id();
-#pragma unroll
-  for (int j = 0; j < kSums; ++j) {
-    const double s = wave_sum(acc[j]);
-    if ((threadIdx.x & 63) == 0) lds[w][j] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kSums) {
-    double s = lds[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < kThreads / 64; ++k) s += lds[k][threadIdx.x];
-    partial[(int64_t)blockIdx.x * kSums + threadIdx.x] = s;
-  }
+__device__ __forceinline__ void store_group_sums(const double (&acc)[kSums], double (*lds)[kSums], double* partial) {
+  const double s = group_sum<kThreads>(acc, lds);
+  if (threadIdx.x < kSums) partial[(int64_t)blockIdx.x * kSums + threadIdx.x] = s;
 }
 
 __global__ __launch_bounds__(kThreads) void k_icp_partials(IcpArgs a) {
@@ -330,21 +320,13 @@ __global__ __launch_bounds__(kThreads) void k_icp_partials(IcpArgs a) {
   store_group_sums(acc, lds, a.partial);
 }
 
-// out[j] = the partials of workgroups 0, 1, ... added in that order.  One wave per sum j: its lanes load 64
-// consecutive workgroups' partials at once, then every lane adds the 64 values in lane order (a shuffle each),
-// so the additions are the serial ones while the loads are 16 rounds, not 1024.
+// out[j] = the partials of workgroups 0, 1, ... added in that order: one wave per sum j
 __global__ __launch_bounds__(64) void k_icp_final(const double* partial, int32_t groups, double* out) {
-  const int j = blockIdx.x, lane = threadIdx.x;
+  const int j = blockIdx.x;
   if (j >= kSums) return;
   groups = groups < kMaxGroups ? groups : kMaxGroups;
-  double s = 0.0;
-  for (int32_t base = 0; base < groups; base += 64) {  // uniform: at most kMaxGroups / 64 rounds
-    const int32_t g = base + lane;
-    const double v = g < groups ? partial[(int64_t)g * kSums + j] : 0.0;
-    const int n = groups - base < 64 ? groups - base : 64;
-    for (int i = 0; i < n; ++i) s += __shfl(v, i, 64);
-  }
-  if (lane == 0) out[j] = s;
+  const double s = wave_ordered_sum(as_global(partial) + j, groups, kSums);
+  if (threadIdx.x == 0) out[j] = s;
 }
 
 // ------------------------------------------------------------------------------------------------

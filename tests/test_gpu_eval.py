@@ -243,6 +243,48 @@ def test_kabsch_sums_match_torch(pkg):
             assert np.abs(g[1:4] - w).max() <= 1e-12 * np.abs(w).max()
 
 
+def _kabsch_partials(src, idx, targets):
+    """The workgroup partials [workgroups, 17] in k_kabsch_sums' order: thread t of workgroup w takes points
+    w · 1024 + k · 256 + t for k = 0..3, forms the 17 values as the kernel writes them (e2 summed over r = 0..2
+    from 0 before it is added), and the workgroup's sums are csrc/nslam_reduce.h's.  A skipped point adds +0."""
+    import ordered_sum_ref as osr
+    n = src.shape[0]
+    wgs = -(-n // 1024)
+    ok = np.zeros(wgs * 1024, bool)
+    ok[:n] = idx >= 0
+    a, b = np.zeros((wgs * 1024, 3)), np.zeros((wgs * 1024, 3))
+    a[:n][ok[:n]] = src[ok[:n]]
+    b[:n][ok[:n]] = targets[idx[ok[:n]]]
+    vals = np.zeros((17, wgs * 1024))
+    vals[0] = ok
+    e2 = np.zeros(wgs * 1024)
+    for r in range(3):
+        vals[1 + r], vals[4 + r] = a[:, r], b[:, r]
+        for c in range(3):
+            vals[7 + 3 * r + c] = a[:, r] * b[:, c]
+        d = a[:, r] - b[:, r]
+        e2 = e2 + d * d
+    vals[16] = e2
+    per_thread = osr.thread_sum(vals.reshape(17, wgs, 4, 256).transpose(2, 0, 1, 3))   # [17, wgs, 256]
+    return osr.group_sum(per_thread).T
+
+
+@pytest.mark.parametrize("n", [1, 63, 1025, 65 * 1024 + 1])
+def test_kabsch_sums_bits_are_the_ordered_sum(pkg, n):
+    """Bit for bit, the host's chain over the workgroup partials included."""
+    import ordered_sum_ref as osr
+    rng = np.random.default_rng([9, n])
+    src, targets = rng.standard_normal((n, 3)), rng.standard_normal((500, 3))
+    idx = rng.integers(0, 500, n).astype(np.int32)
+    idx[rng.random(n) < 0.2] = -1
+    if n == 1:
+        idx[0] = 3
+    got = pkg.ops.kabsch_sums(_t(src), _t(idx), _t(targets))
+    want = osr.ordered_sum(_kabsch_partials(src, idx, targets))
+    assert want[0] == (idx >= 0).sum() > 0
+    assert np.array_equal(osr.bits(got), osr.bits(want)), got - want
+
+
 def test_icp_recovers_the_transform(pkg):
     import eval_scene as S
     src, dst, want = S.icp_scene()

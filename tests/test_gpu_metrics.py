@@ -21,6 +21,7 @@ import torch
 from PIL import Image
 
 import metrics_cases as mc
+import ordered_sum_ref as osr
 
 pytestmark = pytest.mark.gpu
 P = importlib.import_module("nice-slam_amd")
@@ -144,6 +145,54 @@ def test_image_errors(n_pix, C):
         ops.image_errors(d[0], d[1], mask="depth")
     with pytest.raises(ValueError, match="differ in shape"):
         ops.image_errors(d[0], d[1], torch.zeros(B, 1, n_pix + 1, device=DEV), torch.zeros(B, 1, n_pix + 1, device=DEV))
+
+
+def _error_partials(color, gt_color, depth, gt_depth, mode):
+    """One image's workgroup partials [blocks, 4] in k_image_errors' order: workgroup b, thread t and pass q take
+    pixels (q · blocks + b) · 1024 + j · 256 + t for j = 0..3, channels ascending within a pixel; the term is
+    (double)v - (double)gt squared with v clamped in float32.  A pixel that is skipped or past the image adds +0."""
+    n_pix, C = color.shape
+    blocks = min(-(-n_pix // 1024), 1024)
+    passes = -(-n_pix // (blocks * 1024))
+
+    def lay(a):  # [n_pix, ...] -> [passes, blocks, 4, 256, ...], zero past the image
+        full = np.zeros((passes * blocks * 1024,) + a.shape[1:])
+        full[:n_pix] = a
+        return full.reshape((passes, blocks, 4, 256) + a.shape[1:])
+
+    valid = gt_depth > 0
+    counted = valid if mode == 1 else np.ones(n_pix, bool)
+    d = np.clip(color, np.float32(0), np.float32(1)).astype(np.float64) - gt_color.astype(np.float64)
+    sq = lay(np.where(counted[:, None], d * d, 0.0))
+    n_col = lay(np.where(counted, float(C), 0.0))
+    ad = lay(np.where(valid, np.abs(depth.astype(np.float64) - gt_depth.astype(np.float64)), 0.0))
+    n_dep = lay(valid.astype(np.float64))
+    acc = np.zeros((4, blocks, 256))
+    for q in range(passes):
+        for j in range(4):
+            acc[2] = acc[2] + ad[q, :, j]
+            acc[3] = acc[3] + n_dep[q, :, j]
+            for c in range(C):
+                acc[0] = acc[0] + sq[q, :, j, :, c]
+            acc[1] = acc[1] + n_col[q, :, j]
+    return osr.group_sum(acc).T
+
+
+@pytest.mark.parametrize("C", [1, 3])
+@pytest.mark.parametrize("n_pix", [1, 257, 64 * 1024, 64 * 1024 + 1, ERR_SHARE_GRID + 1])
+def test_image_errors_bits_are_the_ordered_sum(n_pix, C):
+    """All four outputs bit for bit: one thread; two waves, one nearly empty; exactly 64 partials; 65 (the ordered
+    sum's second round); the second pass of the grid stride with 1024 partials."""
+    B = 2
+    color, gt_color, depth, gt_depth = mc.error_case(B, 1, n_pix, C, seed=7)
+    d = [dev(a) for a in (color, gt_color, depth, gt_depth)]
+    for mode, name in ((0, "none"), (1, "depth")):
+        got = ops.image_errors(*d, mask=name).cpu().numpy()
+        want = np.stack([osr.ordered_sum(_error_partials(color[b].reshape(n_pix, C), gt_color[b].reshape(n_pix, C),
+                                                         depth[b].ravel(), gt_depth[b].ravel(), mode))
+                         for b in range(B)])
+        assert want[0, 3] > 0 or n_pix == 1
+        assert np.array_equal(osr.bits(got), osr.bits(want)), (name, got - want)
 
 
 def _frame(H, W, seed=4):

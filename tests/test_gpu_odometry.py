@@ -195,6 +195,60 @@ def test_icp_sums_reject_what_the_twin_rejects(pkg, frs, maps):
     assert (ref.accept != base.accept).sum() > 10
 
 
+def _random_maps(H, W, level, seed):
+    """Seeded maps that pass every gate with thresholds wide open: a source vertex map whose pixels project onto
+    themselves under identity poses, the same map with noise as the model / reference, random unit normals, random
+    grey levels.  -> (camera intrinsics, a dict of device tensors)."""
+    rng = np.random.default_rng([seed, H, W, level])
+    fx = fy = 100.0
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    z = 1.0 + rng.random((H, W))
+    v, u = np.mgrid[0:H, 0:W]
+    sv = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], -1)
+
+    def normals():
+        n = rng.standard_normal((H, W, 3))
+        return n / np.linalg.norm(n, axis=-1, keepdims=True)
+
+    S = 1 << level
+    gray = (-(-H // S), -(-W // S))
+    m = dict(sv=sv, sn=normals(), mv=sv + 0.01 * rng.standard_normal(sv.shape), mn=normals(),
+             sg=rng.random(gray), rg=rng.random(gray))
+    return (fx, fy, cx, cy), {k: _dev(a) for k, a in m.items()}
+
+
+@pytest.mark.parametrize("H,W,level", [(16, 16, 0), (128, 128, 0), (130, 130, 0), (130, 130, 1)])
+@pytest.mark.parametrize("entry", ["nslam_icp_sums", "nslam_photo_sums"])
+def test_final_sums_are_the_partials_in_index_order(pkg, entry, H, W, level):
+    """out[j] is, bit for bit, the sequential chain over partial[0..groups-1][j] for all 29 values: 1, 64, 67 and
+    (at stride 2) 17 workgroups.  The terms and the workgroup stage are the twin comparisons' business."""
+    import ctypes
+
+    import ordered_sum_ref as osr
+    import torch
+    L, ptr = pkg._lib.lib(), pkg._lib.ptr
+    intr, m = _random_maps(H, W, level, seed=3)
+    stride = 1 << level
+    groups = int(L.nslam_icp_partials(H, W, stride))
+    assert groups == {(16, 0): 1, (128, 0): 64, (130, 0): 67, (130, 1): 17}[(H, level)]
+    partial = torch.full((groups, 29), float("nan"), dtype=torch.float64, device=DEV)
+    out = torch.full((29,), float("nan"), dtype=torch.float64, device=DEV)
+    eye = (ctypes.c_double * 16)(*np.eye(4).ravel())
+    stream = pkg._lib.stream_ptr(DEV)
+    if entry == "nslam_icp_sums":
+        rc = L.nslam_icp_sums(ptr(m["sv"]), ptr(m["sn"]), H, W, stride, eye, ptr(m["mv"]), ptr(m["mn"]), H, W, eye,
+                              *intr, 1.0e3, -1.0, ptr(partial), groups, ptr(out), None, stream)
+    else:
+        sh, sw = m["sg"].shape
+        rc = L.nslam_photo_sums(ptr(m["sv"]), H, W, ptr(m["sg"]), sh, sw, ptr(m["rg"]), sh, sw, level, ptr(m["mv"]),
+                                H, W, eye, eye, *intr, 1.0e3, 1.0e3, ptr(partial), groups, ptr(out), None, stream)
+    assert rc == 0
+    got, rows = out.cpu().numpy(), partial.cpu().numpy()
+    print(f"{entry} {H}x{W} level {level}: {groups} workgroups, {int(got[28])} accepted pixels")
+    assert got[28] > 0 and np.isfinite(rows).all()               # a row of zeros cannot pass
+    assert np.array_equal(osr.bits(got), osr.bits(osr.ordered_sum(rows))), got - osr.ordered_sum(rows)
+
+
 # ------------------------------------------------------------------------------------------------
 # the tracker
 # ------------------------------------------------------------------------------------------------

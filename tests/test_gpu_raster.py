@@ -211,6 +211,24 @@ def test_depth_l1_matches_torch(pkg, image):
     assert bool(((odd - want).abs() <= 1e-12 * want).all())
 
 
+@pytest.mark.parametrize("n_pix", [1, 63, 64, 65, 255, 256, 257, 1000])
+def test_depth_l1_bits_are_the_ordered_sum(pkg, n_pix):
+    """Bit for bit in k_depth_l1's order: thread t adds pixels t, t + 256, ..., the workgroup's sum is
+    csrc/nslam_reduce.h's, and the total is divided by n_pix in float64."""
+    import ordered_sum_ref as osr
+    rng = np.random.default_rng([5, n_pix])
+    a = (rng.random((3, 1, n_pix)) * 4.0).astype(np.float32)
+    b = (a + 0.05 * rng.standard_normal(a.shape)).astype(np.float32)
+    got = pkg.ops.depth_l1(_t(a), _t(b)).cpu().numpy()
+    rounds = -(-n_pix // 256)
+    terms = np.zeros((3, rounds * 256))                          # a thread past the image adds nothing: +0
+    terms[:, :n_pix] = np.abs(a.astype(np.float64) - b.astype(np.float64)).reshape(3, n_pix)
+    per_thread = osr.thread_sum(terms.reshape(3, rounds, 256).transpose(1, 0, 2))
+    want = osr.group_sum(per_thread) / float(n_pix)
+    assert want.min() > 0
+    assert np.array_equal(osr.bits(got), osr.bits(want)), got - want
+
+
 # ------------------------------------------------------------------------------------------------
 # the view sampler
 # ------------------------------------------------------------------------------------------------

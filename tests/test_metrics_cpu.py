@@ -148,3 +148,27 @@ def test_float32_floors_are_printed_and_small():
                 # over C2 = 9e-4 where the variance vanishes (constant images) — no more than 1e-3 anywhere
                 assert np.all(fl < 1e-3)
                 assert np.all(fl[mc.KINDS.index("same")] == 0.0)
+
+
+def test_ordered_sum_ref_is_the_lane_by_lane_tree():
+    """tests/ordered_sum_ref.py against a lane-by-lane model of the two spellings of the wave tree: in lane 0 the
+    xor butterfly and the shift-down tree add the same operands (a + b and b + a are the same bits), and that is
+    wave_tree; group_sum and ordered_sum against their definitions on values whose order of addition matters."""
+    import ordered_sum_ref as osr
+    rng = np.random.default_rng(1)
+    t = rng.standard_normal(256) * 10.0 ** rng.integers(-8, 8, 256)
+    xor, down = t[:64].copy(), t[:64].copy()
+    lanes = np.arange(64)
+    for d in (32, 16, 8, 4, 2, 1):
+        xor = xor + xor[lanes ^ d]
+        down = down + down[np.where(lanes + d < 64, lanes + d, lanes)]  # past the wave: the lane's own value
+    assert len(set(osr.bits(xor).tolist())) == 1                 # every lane of the butterfly holds the same bits
+    assert osr.bits(osr.wave_tree(t[:64])) == osr.bits(xor[0]) == osr.bits(down[0])
+    assert osr.bits(osr.wave_tree(t[:64])) != osr.bits(osr.ordered_sum(t[:64]))  # and the order matters here
+    w = [osr.wave_tree(t[64 * k:64 * k + 64]) for k in range(4)]
+    assert osr.group_sum(t) == ((w[0] + w[1]) + w[2]) + w[3]
+    s = 0.0
+    for v in t:
+        s = s + v
+    assert osr.ordered_sum(t) == s and osr.ordered_sum(t[:0]) == 0.0
+    assert np.array_equal(osr.ordered_sum(np.stack([t, -t])), np.zeros(256))
