@@ -13,12 +13,21 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NSLAM_LIB") or os.path.join(_HERE, "libnslam.so")  # NSLAM_LIB: instrumented builds
 
-NSLAM_OK = 0
 ABI_VERSION = 24
-STAGES = {"coarse": 0, "middle": 1, "fine": 2, "color": 3}
-DEC_COARSE, DEC_MIDDLE, DEC_FINE, DEC_COLOR = 0, 1, 2, 3
 
-c_float_p = ctypes.POINTER(ctypes.c_float)
+# The named values of include/nslam.h (NSLAM_<name>).  This module is the only place that restates them: the
+# rest of the package imports them from here, and tests/test_abi_cpu.py compiles the header and compares each.
+NSLAM_OK, NSLAM_EINVAL, NSLAM_EUNSUPPORTED, NSLAM_EWORKSPACE, NSLAM_EHIP = 0, -1, -2, -3, -1000
+EMB = 93
+STAGES = {"coarse": 0, "middle": 1, "fine": 2, "color": 3}  # NSLAM_STAGE_*
+DEC_COARSE, DEC_MIDDLE, DEC_FINE, DEC_COLOR = 0, 1, 2, 3
+MAX_FRAMES = 32  # of nslam_gather_rays, the camera batches and the TSDF touch / integrate calls
+LOSS_MAPPER, LOSS_TRACKER = 0, 1
+ADAM_MAX_SEGS = 16
+CAM_GRAD_WS_DOUBLES = 32 * 12
+RASTER_CLEAR, RASTER_SMALL, RASTER_BIG, RASTER_RESOLVE, RASTER_ALL = 1, 2, 4, 8, 15
+CULL_MODES = {"none": 0, "back": 1, "front": 2}  # NSLAM_CULL_*
+SCENE_POINTS, SCENE_ALL = 16, 31
 
 
 class NslamGrid(ctypes.Structure):
@@ -66,11 +75,6 @@ class NslamQueryCfg(ctypes.Structure):
         ("act_tape", ctypes.c_void_p),  # ABI v9: colour-decoder activation tape (NULL = none)
         ("g_h4", ctypes.c_void_p),  # ABI v17: colour decoder's d/dh4 [M][32] (NULL = none)
     ]
-
-
-MAX_FRAMES = 32
-ADAM_MAX_SEGS = 16
-LOSS_MAPPER, LOSS_TRACKER = 0, 1
 
 
 class NslamFrame(ctypes.Structure):
@@ -134,55 +138,137 @@ class NslamImapQuery(ctypes.Structure):
                 ("bound_hi", ctypes.c_double * 3)]
 
 
-# every symbol include/nslam.h declares (tests check that the library exports all of them)
-EXPORTS = (
-    "nslam_pack_layout", "nslam_sample_rays", "nslam_query_fwd", "nslam_query_bwd", "nslam_query_bwd_workspace_size",
-    "nslam_query_saved_size", "nslam_query_bwd_decoder", "nslam_query_bwd_decoder_workspace_size",
-    "nslam_query_bwd_decoders",
-    "nslam_composite_fwd", "nslam_composite_bwd", "nslam_grid_sample_fwd", "nslam_grid_sample_bwd",
-    "nslam_workspace_size", "nslam_strerror", "nslam_abi_version", "nslam_gather_rays", "nslam_render_loss",
-    "nslam_render_loss_workspace_size", "nslam_adam_step", "nslam_rows_pack", "nslam_rows_unpack",
-    "nslam_query_fwd_ws", "nslam_query_fwd_workspace_size", "nslam_cam_grad", "nslam_cam_pose",
-    "nslam_query_tape_size", "nslam_color_wgrad", "nslam_cam_grad_parts", "nslam_cam_grad_batch",
-    "nslam_cam_pose_batch", "nslam_frustum_rows", "nslam_frustum_rows_workspace_size",
-    "nslam_loss_sum_best", "nslam_cam_vector_batch", "nslam_cam_grad_step",
-    # mesh extraction (additive: no ABI bump)
-    "nslam_point_masks", "nslam_point_masks_workspace_size", "nslam_mc_count", "nslam_mc_emit",
-    "nslam_mc_workspace_size", "nslam_points_in_hull", "nslam_mesh_face_cull", "nslam_mesh_components",
-    "nslam_mesh_select", "nslam_mesh_remap",
+# short names of the table below: vp is a device buffer (or the stream), the typed pointers are host arrays
+P = ctypes.POINTER
+ci, i32, i64, u64, sz = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t
+f32, f64, vp = ctypes.c_float, ctypes.c_double, ctypes.c_void_p
+i32p, i64p, u8p, f32p, dp, vpp = P(i32), P(i64), P(ctypes.c_uint8), P(f32), P(f64), P(vp)
+qcfg, ipp, iqp = P(NslamQueryCfg), P(NslamImapParams), P(NslamImapQuery)
+
+# Every entry point include/nslam.h declares, in the header's order: name -> (restype, argtypes).  Adding one is
+# its prototype in the header and its line here; tests/test_abi_cpu.py parses the header and compares the two.
+SIGNATURES = {
+    "nslam_pack_layout": (ci, [ci, ci, i32p, ci]),
+    "nslam_sample_rays": (ci, [vp, vp, vp, vp, i64, dp, dp, vp, i32, vp, i32, i32, vp, vp, sz, vp]),
+    "nslam_query_fwd": (ci, [qcfg, vp, i64, vp, vp]),
+    "nslam_query_fwd_ws": (ci, [qcfg, vp, i64, vp, vp, sz, vp]),
+    "nslam_query_fwd_workspace_size": (sz, [qcfg, i64]),
+    "nslam_query_bwd": (ci, [qcfg, vp, i64, vp, vp, vp, sz, vp]),
+    "nslam_query_bwd_workspace_size": (sz, [qcfg, i64]),
+    "nslam_query_bwd_decoder": (ci, [qcfg, i32, i32, vp, i64, vp, vp, vp, sz, vp]),
+    "nslam_query_bwd_decoder_workspace_size": (sz, [qcfg, i32, i64]),
+    "nslam_query_saved_size": (sz, [i64]),
+    "nslam_query_tape_size": (sz, [i64]),
+    "nslam_query_bwd_decoders": (ci, [qcfg, i32, vp, i64, vp, vpp, vp]),
     # live-point lists of the mask-only mapping backward (additive: no ABI bump)
-    "nslam_live_points", "nslam_live_points_workspace_size", "nslam_query_bwd_decoders_live",
-    # evaluation: frustum culling, surface samples, nearest neighbours, ICP sums (additive: no ABI bump)
-    "nslam_frustum_seen", "nslam_face_areas", "nslam_sample_surface", "nslam_nn_build", "nslam_nn_query",
-    "nslam_transform_points", "nslam_kabsch_sums", "nslam_kabsch_partials",
-    # depth L1: mesh rasteriser, view rejection, per-view error (additive: no ABI bump)
-    "nslam_raster_depth", "nslam_raster_workspace_size", "nslam_views_see_any", "nslam_depth_l1",
-    # TUM-RGBD: lens undistortion, separate learning rates on the fused camera tail (additive: no ABI bump)
-    "nslam_undistort_u8", "nslam_cam_grad_step_lr2",
-    # iMAP*: the 256-wide Fourier MLP, density compositing, the hierarchical sampler (additive: no ABI bump)
-    "nslam_imap_packed_size", "nslam_imap_pack", "nslam_imap_tape_size", "nslam_imap_fwd",
-    "nslam_imap_bwd_workspace_size", "nslam_imap_bwd", "nslam_composite_density_fwd",
-    "nslam_composite_density_bwd", "nslam_sample_importance",
-    # the visualiser's panel mosaic (additive: no ABI bump)
-    "nslam_vis_panels",
-    # replay: the scene renderer of visualizer.py's frames (additive: no ABI bump)
-    "nslam_scene_render", "nslam_scene_workspace_size",
+    "nslam_live_points": (ci, [qcfg, i32, vp, i64, vpp, vpp, vp, sz, vp]),
+    "nslam_live_points_workspace_size": (sz, [i64]),
+    "nslam_query_bwd_decoders_live": (ci, [qcfg, i32, vp, i64, vp, vpp, vpp, vp]),
+    "nslam_color_wgrad": (ci, [qcfg, vp, i64, vp, vp, sz, vp]),
+    "nslam_composite_fwd": (ci, [vp, vp, i64, i32, vp, vp, vp, vp]),
+    "nslam_composite_bwd": (ci, [vp, vp, i64, i32, vp, vp, vp, vp, vp]),
+    "nslam_grid_sample_fwd": (ci, [vp, i32p, vp, i64, vp, vp]),
+    "nslam_grid_sample_bwd": (ci, [vp, i32p, vp, i64, vp, vp, vp, vp]),
+    "nslam_gather_rays": (ci, [P(NslamFrame), i32, i64, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, dp, dp,
+                               vp, vp, vp, vp, vp, P(NslamDraw), vp, vp]),
+    "nslam_render_loss": (ci, [P(NslamLossCfg), vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "nslam_render_loss_workspace_size": (sz, [P(NslamLossCfg), i64]),
+    "nslam_adam_step": (ci, [P(NslamAdamSeg), i32, f32, f32, f32, i32, vp, vp]),
+    "nslam_rows_pack": (ci, [vp, vp, i64, i32, vp, i64, vp, vp]),
+    "nslam_rows_unpack": (ci, [vp, vp, i64, i32, vp, vp, i64, vp]),
+    "nslam_cam_grad": (ci, [vp, vp, vp, vp, vp, i64, i32, vp, vp]),
+    "nslam_cam_grad_parts": (ci, [vp, vp, vpp, i32, vp, vp, i64, i32, vp, vp, vp, vp]),
+    "nslam_cam_grad_batch": (ci, [vp, vp, i64, i32, i64p, i64, vpp, i32, vp, vp, i64, i32, vp, vp, vp, vp]),
+    "nslam_cam_grad_step": (ci, [P(NslamCamTail), vp, vpp, i32, vp, vp, i64, i32, vp, vp, vp, vp]),
+    # TUM-RGBD: separate learning rates on the fused camera tail (additive: no ABI bump)
+    "nslam_cam_grad_step_lr2": (ci, [P(NslamCamTailLr2), vp, vpp, i32, vp, vp, i64, i32, vp, vp, vp, vp]),
+    "nslam_cam_pose_batch": (ci, [vp, vp, i64, i32, vp]),
+    "nslam_frustum_rows": (ci, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "nslam_frustum_rows_workspace_size": (sz, [i64]),
+    "nslam_loss_sum_best": (ci, [vp, i64, vp, vp, vp, vp, i32, vp]),
+    "nslam_cam_vector_batch": (ci, [vp, i64, i32, vp, vp, vp]),
+    "nslam_cam_pose": (ci, [vp, vp, vp]),
+    # mesh extraction (additive: no ABI bump)
+    "nslam_point_masks": (ci, [vp, i64, vp, i32, vp, i32, i32, f32, f32, f32, f32, i32, i32, i64, vp, vp, vp, vp, sz,
+                               vp]),
+    "nslam_point_masks_workspace_size": (sz, [i64, i32, i64]),
+    "nslam_mc_count": (ci, [vp, i32, i32, i32, f32, vp, sz, vp]),
+    "nslam_mc_emit": (ci, [vp, i32, i32, i32, f32, dp, dp, vp, vp, i64, i64, vp, vp, vp]),
+    "nslam_mc_workspace_size": (sz, [i32, i32, i32]),
+    "nslam_points_in_hull": (ci, [vp, i32, i64, vp, i32, vp, vp]),
+    "nslam_mesh_face_cull": (ci, [vp, i64, vp, i64, vp, vp]),
+    "nslam_mesh_components": (ci, [vp, i64, vp, i64, vp, vp, vp, vp]),
+    "nslam_mesh_select": (ci, [vp, i64, vp, vp, vp, f64, vp, vp, vp]),
+    "nslam_mesh_remap": (ci, [vp, i64, vp, vp, vp]),
     # TSDF fusion: block range, touch masks, integration, marching cubes over the pool (additive: no ABI bump)
-    "nslam_tsdf_block_range", "nslam_tsdf_touch", "nslam_tsdf_integrate", "nslam_tsdf_mc_count",
-    "nslam_tsdf_mc_emit",
+    "nslam_tsdf_block_range": (ci, [vp, vp, i32, i32, i32, f64, f64, f64, f64, i32, f32, f64, f64, vp, vp, vp]),
+    "nslam_tsdf_touch": (ci, [vp, vp, i32, i32, i32, f64, f64, f64, f64, i32, f32, f64, f64, i32p, i32p, vp, vp, vp]),
+    "nslam_tsdf_integrate": (ci, [vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, f64, f32, i32p, i32p, vp, vp,
+                                  vp, i64, i64, vp, vp, vp, i64, vp]),
+    "nslam_tsdf_mc_count": (ci, [vp, vp, vp, i64, vp, i32p, i32p, vp, vp, vp]),
+    "nslam_tsdf_mc_emit": (ci, [vp, vp, vp, i64, vp, i64, vp, i32p, i32p, f64, vp, vp, vp, vp, i64, i64, vp, vp, vp,
+                                vp]),
     # depth odometry: depth maps, the volume's ray cast, ICP sums (additive: no ABI bump)
-    "nslam_depth_maps", "nslam_tsdf_raycast", "nslam_icp_partials", "nslam_icp_sums",
+    "nslam_depth_maps": (ci, [vp, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp, vp]),
+    "nslam_tsdf_raycast": (ci, [vp, vp, vp, vp, i64, i32p, i32p, f64, f64, dp, i32, i32, f64, f64, f64, f64, f64, f64,
+                                vp, vp, vp]),
+    "nslam_icp_partials": (i64, [i32, i32, i32]),
+    "nslam_icp_sums": (ci, [vp, vp, i32, i32, i32, dp, vp, vp, i32, i32, dp, f64, f64, f64, f64, f64, f64, vp, i64,
+                            vp, vp, vp]),
     # its photometric term: grey pyramid, photometric sums (additive: no ABI bump)
-    "nslam_gray_pyramid_size", "nslam_gray_pyramid", "nslam_photo_sums",
+    "nslam_gray_pyramid_size": (i64, [i32, i32, i32]),
+    "nslam_gray_pyramid": (ci, [vp, i32, i32, i32, vp, vp]),
+    "nslam_photo_sums": (ci, [vp, i32, i32, vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, dp, dp, f64, f64, f64, f64,
+                              f64, f64, vp, i64, vp, vp, vp]),
+    # evaluation: frustum culling, surface samples, nearest neighbours, ICP sums (additive: no ABI bump)
+    "nslam_frustum_seen": (ci, [vp, i64, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp]),
+    "nslam_face_areas": (ci, [vp, i64, vp, i64, vp, vp]),
+    "nslam_sample_surface": (ci, [vp, i64, vp, vp, i64, i64, u64, vp, vp, vp]),
+    "nslam_nn_build": (ci, [vp, i64, dp, f64, i32p, vp, vp]),
+    "nslam_nn_query": (ci, [vp, i64, vp, vp, i64, vp, i64, dp, f64, i32p, f64, vp, vp, vp]),
+    "nslam_transform_points": (ci, [vp, i64, dp, vp, vp]),
+    "nslam_kabsch_sums": (ci, [vp, vp, i64, vp, i64, vp, i64, vp]),
+    "nslam_kabsch_partials": (i64, [i64]),
+    # depth L1: view rejection, per-view error, mesh rasteriser (additive: no ABI bump)
+    "nslam_views_see_any": (ci, [vp, i64, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp]),
+    "nslam_depth_l1": (ci, [vp, vp, i64, i64, vp, vp]),
+    "nslam_raster_depth": (ci, [vp, i64, vp, i64, vp, i32, i32, i32, f64, f64, f64, f64, f64, f64, i64, i32, vp, vp,
+                                sz, vp]),
+    "nslam_raster_workspace_size": (sz, [i64]),
+    # replay: the scene renderer of visualizer.py's frames (additive: no ABI bump)
+    "nslam_scene_render": (ci, [vp, i64, vp, i64, vp, vp, i32, u8p, vp, vp, i64, f64, vp, i32, i32, i32, f64, f64, f64,
+                                f64, f64, f64, i32, u8p, f64, i64, i32, vp, vp, vp, vp, sz, vp]),
+    "nslam_scene_workspace_size": (sz, [i64, i32, i32, i32]),
+    # TUM-RGBD: lens undistortion (additive: no ABI bump)
+    "nslam_undistort_u8": (ci, [vp, i32, i32, i32, f64, f64, f64, f64, dp, vp, vp]),
+    # the visualiser's panel mosaic (additive: no ABI bump)
+    "nslam_vis_panels": (ci, [vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    # iMAP*: the 256-wide Fourier MLP, density compositing, the hierarchical sampler (additive: no ABI bump)
+    "nslam_imap_packed_size": (sz, []),
+    "nslam_imap_pack": (ci, [ipp, vp, vp]),
+    "nslam_imap_tape_size": (sz, [i64]),
+    "nslam_imap_fwd": (ci, [ipp, vp, iqp, i64, vp, vp, vp]),
+    "nslam_imap_bwd_workspace_size": (sz, [i64]),
+    "nslam_imap_bwd": (ci, [ipp, vp, iqp, i64, vp, vp, ipp, vp, vp, sz, vp]),
+    "nslam_composite_density_fwd": (ci, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
+    "nslam_composite_density_bwd": (ci, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]),
+    "nslam_sample_importance": (ci, [vp, vp, vp, i64, i32, i32, vp, vp, vp]),
     # rendering evaluation: PSNR / depth-L1 sums, SSIM and MS-SSIM means (additive: no ABI bump)
-    "nslam_image_errors", "nslam_image_errors_workspace_size", "nslam_ssim", "nslam_ssim_workspace_size",
-)
+    "nslam_image_errors_workspace_size": (sz, [i32, i64]),
+    "nslam_image_errors": (ci, [vp, vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, sz, vp]),
+    "nslam_ssim_workspace_size": (sz, [i32, i32, i32, i32, i32]),
+    "nslam_ssim": (ci, [vp, vp, i32, i32, i32, i32, f64, f32p, i32, vp, vp, sz, vp]),
+    "nslam_workspace_size": (sz, [ci, i64]),
+    "nslam_strerror": (ctypes.c_char_p, [ci]),
+    "nslam_abi_version": (ci, []),
+}
+EXPORTS = tuple(SIGNATURES)
 
 _lib = None
 
 
 def lib():
-    """Load libnslam.so once (fails loudly when it has not been built)."""
+    """Load libnslam.so once (fails loudly when it has not been built) and bind SIGNATURES."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -195,142 +281,9 @@ def lib():
         if missing:
             raise RuntimeError(f"{LIB_PATH} does not export {', '.join(missing)}: rebuild it "
                                "(make -C nice-slam_amd/csrc)")
-        vp, i32, i64, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
-        dp = ctypes.POINTER(ctypes.c_double)
-        L.nslam_pack_layout.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]
-        L.nslam_sample_rays.argtypes = [vp, vp, vp, vp, i64, dp, dp, vp, i32, vp, i32, i32, vp, vp, sz, vp]
-        L.nslam_query_fwd.argtypes = [ctypes.POINTER(NslamQueryCfg), vp, i64, vp, vp]
-        L.nslam_query_fwd_ws.argtypes = [ctypes.POINTER(NslamQueryCfg), vp, i64, vp, vp, sz, vp]
-        L.nslam_query_fwd_workspace_size.argtypes = [ctypes.POINTER(NslamQueryCfg), i64]
-        L.nslam_query_fwd_workspace_size.restype = sz
-        L.nslam_query_bwd.argtypes = [ctypes.POINTER(NslamQueryCfg), vp, i64, vp, vp, vp, sz, vp]
-        L.nslam_query_bwd_workspace_size.argtypes = [ctypes.POINTER(NslamQueryCfg), i64]
-        L.nslam_query_bwd_workspace_size.restype = sz
-        L.nslam_query_bwd_decoder.argtypes = [ctypes.POINTER(NslamQueryCfg), i32, i32, vp, i64, vp, vp, vp, sz, vp]
-        L.nslam_query_bwd_decoders.argtypes = [ctypes.POINTER(NslamQueryCfg), i32, vp, i64, vp, ctypes.POINTER(vp), vp]
-        L.nslam_color_wgrad.argtypes = [ctypes.POINTER(NslamQueryCfg), vp, i64, vp, vp, sz, vp]
-        L.nslam_query_bwd_decoder_workspace_size.argtypes = [ctypes.POINTER(NslamQueryCfg), i32, i64]
-        L.nslam_query_bwd_decoder_workspace_size.restype = sz
-        L.nslam_query_saved_size.argtypes = [i64]
-        L.nslam_query_saved_size.restype = sz
-        L.nslam_query_tape_size.argtypes = [i64]
-        L.nslam_query_tape_size.restype = sz
-        L.nslam_composite_fwd.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
-        L.nslam_composite_bwd.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp]
-        L.nslam_grid_sample_fwd.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), vp, i64, vp, vp]
-        L.nslam_grid_sample_bwd.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), vp, i64, vp, vp, vp, vp]
-        L.nslam_workspace_size.argtypes = [ctypes.c_int, i64]
-        L.nslam_workspace_size.restype = sz
-        L.nslam_strerror.argtypes = [ctypes.c_int]
-        L.nslam_strerror.restype = ctypes.c_char_p
-        L.nslam_abi_version.restype = ctypes.c_int
-        f32 = ctypes.c_float
-        L.nslam_gather_rays.argtypes = [ctypes.POINTER(NslamFrame), i32, i64, vp, i32, i32, i32, i32, i32, i32,
-                                        f32, f32, f32, f32, dp, dp, vp, vp, vp, vp, vp, ctypes.POINTER(NslamDraw), vp, vp]
-        L.nslam_render_loss.argtypes = [ctypes.POINTER(NslamLossCfg), vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp,
-                                        vp, vp, sz, vp]
-        L.nslam_render_loss_workspace_size.argtypes = [ctypes.POINTER(NslamLossCfg), i64]
-        L.nslam_render_loss_workspace_size.restype = sz
-        L.nslam_adam_step.argtypes = [ctypes.POINTER(NslamAdamSeg), i32, f32, f32, f32, i32, vp, vp]
-        L.nslam_rows_pack.argtypes = [vp, vp, i64, i32, vp, i64, vp, vp]
-        L.nslam_rows_unpack.argtypes = [vp, vp, i64, i32, vp, vp, i64, vp]
-        L.nslam_cam_grad.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp]
-        L.nslam_cam_grad_parts.argtypes = [vp, vp, ctypes.POINTER(vp), i32, vp, vp, i64, i32, vp, vp, vp, vp]
-        L.nslam_cam_pose.argtypes = [vp, vp, vp]
-        L.nslam_cam_grad_batch.argtypes = [vp, vp, i64, i32, ctypes.POINTER(i64), i64, ctypes.POINTER(vp), i32, vp, vp,
-                                           i64, i32, vp, vp, vp, vp]
-        L.nslam_cam_pose_batch.argtypes = [vp, vp, i64, i32, vp]
-        L.nslam_frustum_rows.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
-        L.nslam_frustum_rows_workspace_size.argtypes = [i64]
-        L.nslam_frustum_rows_workspace_size.restype = sz
-        L.nslam_loss_sum_best.argtypes = [vp, i64, vp, vp, vp, vp, i32, vp]
-        L.nslam_cam_vector_batch.argtypes = [vp, i64, i32, vp, vp, vp]
-        L.nslam_cam_grad_step.argtypes = [ctypes.POINTER(NslamCamTail), vp, ctypes.POINTER(vp), i32, vp, vp, i64, i32,
-                                          vp, vp, vp, vp]
-        f64 = ctypes.c_double
-        L.nslam_point_masks.argtypes = [vp, i64, vp, i32, vp, i32, i32, f32, f32, f32, f32, i32, i32, i64, vp, vp, vp,
-                                        vp, sz, vp]
-        L.nslam_point_masks_workspace_size.argtypes = [i64, i32, i64]
-        L.nslam_point_masks_workspace_size.restype = sz
-        L.nslam_mc_count.argtypes = [vp, i32, i32, i32, f32, vp, sz, vp]
-        L.nslam_mc_emit.argtypes = [vp, i32, i32, i32, f32, dp, dp, vp, vp, i64, i64, vp, vp, vp]
-        L.nslam_mc_workspace_size.argtypes = [i32, i32, i32]
-        L.nslam_mc_workspace_size.restype = sz
-        L.nslam_points_in_hull.argtypes = [vp, i32, i64, vp, i32, vp, vp]
-        L.nslam_mesh_face_cull.argtypes = [vp, i64, vp, i64, vp, vp]
-        L.nslam_mesh_components.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp]
-        L.nslam_mesh_select.argtypes = [vp, i64, vp, vp, vp, f64, vp, vp, vp]
-        L.nslam_mesh_remap.argtypes = [vp, i64, vp, vp, vp]
-        L.nslam_live_points.argtypes = [ctypes.POINTER(NslamQueryCfg), i32, vp, i64, ctypes.POINTER(vp),
-                                        ctypes.POINTER(vp), vp, sz, vp]
-        L.nslam_live_points_workspace_size.argtypes = [i64]
-        L.nslam_live_points_workspace_size.restype = sz
-        L.nslam_query_bwd_decoders_live.argtypes = [ctypes.POINTER(NslamQueryCfg), i32, vp, i64, vp,
-                                                    ctypes.POINTER(vp), ctypes.POINTER(vp), vp]
-        u64, i32p = ctypes.c_uint64, ctypes.POINTER(ctypes.c_int32)
-        L.nslam_frustum_seen.argtypes = [vp, i64, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp]
-        L.nslam_face_areas.argtypes = [vp, i64, vp, i64, vp, vp]
-        L.nslam_sample_surface.argtypes = [vp, i64, vp, vp, i64, i64, u64, vp, vp, vp]
-        L.nslam_nn_build.argtypes = [vp, i64, dp, f64, i32p, vp, vp]
-        L.nslam_nn_query.argtypes = [vp, i64, vp, vp, i64, vp, i64, dp, f64, i32p, f64, vp, vp, vp]
-        L.nslam_transform_points.argtypes = [vp, i64, dp, vp, vp]
-        L.nslam_kabsch_sums.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp]
-        L.nslam_kabsch_partials.argtypes = [i64]
-        L.nslam_kabsch_partials.restype = i64
-        L.nslam_raster_depth.argtypes = [vp, i64, vp, i64, vp, i32, i32, i32, f64, f64, f64, f64, f64, f64, i64, i32,
-                                         vp, vp, sz, vp]
-        L.nslam_raster_workspace_size.argtypes = [i64]
-        L.nslam_raster_workspace_size.restype = sz
-        L.nslam_views_see_any.argtypes = [vp, i64, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp]
-        L.nslam_depth_l1.argtypes = [vp, vp, i64, i64, vp, vp]
-        L.nslam_undistort_u8.argtypes = [vp, i32, i32, i32, f64, f64, f64, f64, dp, vp, vp]
-        L.nslam_cam_grad_step_lr2.argtypes = [ctypes.POINTER(NslamCamTailLr2), vp, ctypes.POINTER(vp), i32, vp, vp,
-                                              i64, i32, vp, vp, vp, vp]
-        ipp, iqp = ctypes.POINTER(NslamImapParams), ctypes.POINTER(NslamImapQuery)
-        L.nslam_imap_packed_size.argtypes = []
-        L.nslam_imap_packed_size.restype = sz
-        L.nslam_imap_pack.argtypes = [ipp, vp, vp]
-        L.nslam_imap_tape_size.argtypes = [i64]
-        L.nslam_imap_tape_size.restype = sz
-        L.nslam_imap_fwd.argtypes = [ipp, vp, iqp, i64, vp, vp, vp]
-        L.nslam_imap_bwd_workspace_size.argtypes = [i64]
-        L.nslam_imap_bwd_workspace_size.restype = sz
-        L.nslam_imap_bwd.argtypes = [ipp, vp, iqp, i64, vp, vp, ipp, vp, vp, sz, vp]
-        L.nslam_composite_density_fwd.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
-        L.nslam_composite_density_bwd.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
-        L.nslam_sample_importance.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
-        L.nslam_vis_panels.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
-        u8x3 = ctypes.POINTER(ctypes.c_uint8)
-        L.nslam_scene_render.argtypes = [vp, i64, vp, i64, vp, vp, i32, u8x3, vp, vp, i64, f64, vp, i32, i32, i32, f64,
-                                         f64, f64, f64, f64, f64, i32, u8x3, f64, i64, i32, vp, vp, vp, vp, sz, vp]
-        L.nslam_scene_workspace_size.argtypes = [i64, i32, i32, i32]
-        L.nslam_scene_workspace_size.restype = sz
-        L.nslam_tsdf_block_range.argtypes = [vp, vp, i32, i32, i32, f64, f64, f64, f64, i32, f32, f64, f64, vp, vp, vp]
-        L.nslam_tsdf_touch.argtypes = [vp, vp, i32, i32, i32, f64, f64, f64, f64, i32, f32, f64, f64, i32p, i32p, vp,
-                                       vp, vp]
-        L.nslam_tsdf_integrate.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, f64, f32, i32p, i32p,
-                                           vp, vp, vp, i64, i64, vp, vp, vp, i64, vp]
-        L.nslam_tsdf_mc_count.argtypes = [vp, vp, vp, i64, vp, i32p, i32p, vp, vp, vp]
-        L.nslam_tsdf_mc_emit.argtypes = [vp, vp, vp, i64, vp, i64, vp, i32p, i32p, f64, vp, vp, vp, vp, i64, i64, vp,
-                                         vp, vp, vp]
-        L.nslam_depth_maps.argtypes = [vp, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp, vp]
-        L.nslam_tsdf_raycast.argtypes = [vp, vp, vp, vp, i64, i32p, i32p, f64, f64, dp, i32, i32, f64, f64, f64, f64,
-                                         f64, f64, vp, vp, vp]
-        L.nslam_icp_partials.argtypes = [i32, i32, i32]
-        L.nslam_icp_partials.restype = i64
-        L.nslam_icp_sums.argtypes = [vp, vp, i32, i32, i32, dp, vp, vp, i32, i32, dp, f64, f64, f64, f64, f64, f64,
-                                     vp, i64, vp, vp, vp]
-        L.nslam_gray_pyramid_size.argtypes = [i32, i32, i32]
-        L.nslam_gray_pyramid_size.restype = i64
-        L.nslam_gray_pyramid.argtypes = [vp, i32, i32, i32, vp, vp]
-        L.nslam_photo_sums.argtypes = [vp, i32, i32, vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, dp, dp, f64, f64,
-                                       f64, f64, f64, f64, vp, i64, vp, vp, vp]
-        L.nslam_image_errors_workspace_size.argtypes = [i32, i64]
-        L.nslam_image_errors_workspace_size.restype = sz
-        L.nslam_image_errors.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, sz, vp]
-        L.nslam_ssim_workspace_size.argtypes = [i32, i32, i32, i32, i32]
-        L.nslam_ssim_workspace_size.restype = sz
-        L.nslam_ssim.argtypes = [vp, vp, i32, i32, i32, i32, f64, c_float_p, i32, vp, vp, sz, vp]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if L.nslam_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libnslam.so ABI {L.nslam_abi_version()} != {ABI_VERSION}: rebuild it")
         _lib = L

@@ -5,11 +5,8 @@ import torch
 
 from . import span
 from .. import _lib
-from .._lib import check, lib, ptr, stream_ptr
+from .._lib import CAM_GRAD_WS_DOUBLES, check, lib, ptr, stream_ptr
 from ._check import _expect
-
-
-CAM_GRAD_WS_DOUBLES = 32 * 12  # NSLAM_CAM_GRAD_WS_DOUBLES
 
 
 def cam_pose(cam, out):

@@ -3,11 +3,12 @@ import ctypes
 
 import torch
 
-from .._lib import check, lib, ptr, stream_ptr
+# the header's pass flags and cull modes are _lib's (re-exported here: ops.RASTER_*, ops.SCENE_*, ops.CULL_MODES)
+from .._lib import (CULL_MODES, RASTER_ALL, RASTER_BIG, RASTER_CLEAR, RASTER_RESOLVE, RASTER_SMALL,  # noqa: F401
+                    SCENE_ALL, SCENE_POINTS, check, lib, ptr, stream_ptr)
 from ._check import _on_device, _want, _want_mesh
 
 
-RASTER_CLEAR, RASTER_SMALL, RASTER_BIG, RASTER_RESOLVE, RASTER_ALL = 1, 2, 4, 8, 15
 RASTER_SMALL_MAX_PIXELS = 64     # a larger pixel box goes to the list pass (how it was chosen)
 RASTER_WS_BYTES = 64 << 20       # the list's byte budget: 8 M items of 8 bytes
 RASTER_MAX_VIEWS = 65535         # views per launch (one grid row each)
@@ -70,8 +71,6 @@ def raster_list_length(ws):
     return int(ws[:8].view(torch.int64)[0])
 
 
-SCENE_POINTS, SCENE_ALL = 16, 31
-CULL_MODES = {"none": 0, "back": 1, "front": 2}
 SCENE_MAX_POINT_SIZE = 64
 
 

@@ -21,7 +21,7 @@ import torch
 from . import _lib
 
 FRAG = 1024
-EMB = 93
+EMB = _lib.EMB
 
 
 def F(s, h):

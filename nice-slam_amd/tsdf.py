@@ -17,10 +17,10 @@ import numpy as np
 import torch
 
 from . import ops
+from ._lib import MAX_FRAMES  # frames per touch / integrate call (one bit each)
 
 BLOCK = 16
 BLOCK_VOXELS = BLOCK ** 3
-MAX_FRAMES = 32          # frames per touch / integrate call (one bit each)
 MAX_CELLS = 1 << 27      # block-table cells
 
 

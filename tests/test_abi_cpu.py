@@ -77,6 +77,18 @@ _C_STRUCTS = {
 }
 
 
+def _run_probe(tmp_path, statements):
+    """Compile the statements as the body of a C main that includes nslam.h (gcc), run it → its output lines."""
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nslam.h"', "int main(void) {"]
+    lines += list(statements) + ["  return 0; }"]
+    src = tmp_path / "probe.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "probe"
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
+    return [l for l in out if l]
+
+
 def test_struct_layouts_match_header(pkg, tmp_path):
     """sizeof/offsetof of every ABI struct, compiled by gcc from include/nslam.h, equal the ctypes
     mirrors in _lib.py: every ctypes.Structure the module defines, under each C name it mirrors."""
@@ -89,18 +101,12 @@ def test_struct_layouts_match_header(pkg, tmp_path):
                                    "nslam_adam_seg", "nslam_draw"} <= set(structs)
     header = open(os.path.join(REPO, "include", "nslam.h")).read()
     assert set(re.findall(r"^\} *(nslam_\w+);", header, re.M)) == set(structs)  # every struct typedef of the header
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nslam.h"', "int main(void) {"]
+    lines = []
     for cname, py in structs.items():
         lines.append(f'  printf("{cname} size %zu\\n", sizeof({cname}));')
         for f in py._fields_:
             lines.append(f'  printf("{cname} {f[0]} %zu\\n", offsetof({cname}, {f[0]}));')
-    lines.append("  return 0; }")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    got = {tuple(l.split()[:2]): int(l.split()[2]) for l in out if l}
+    got = {tuple(l.split()[:2]): int(l.split()[2]) for l in _run_probe(tmp_path, lines)}
     for cname, py in structs.items():
         assert got[(cname, "size")] == ctypes.sizeof(py), cname
         for f in py._fields_:
@@ -114,6 +120,147 @@ def test_every_export_has_a_declared_signature(pkg):
     for name in pkg._lib.EXPORTS:
         if name != "nslam_abi_version":
             assert getattr(L, name).argtypes is not None, name
+
+
+def _header_text():
+    """include/nslam.h without its comments."""
+    txt = open(os.path.join(REPO, "include", "nslam.h")).read()
+    return re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", txt, flags=re.S))
+
+
+def _header_prototypes():
+    """Every top-level prototype `ret nslam_name(params);` of the header (several lines, or `void`, included) →
+    [(name, ret, [(base type, pointer depth), ...])].  const and a leading struct are dropped; `name[3]` is a
+    pointer; ret keeps its stars ("const char*" → "char*")."""
+    def ctype(text):
+        words = [w for w in text.replace("*", " ").split() if w not in ("const", "struct")]
+        return " ".join(words), text.count("*")
+
+    protos = []
+    prototype = r"^([A-Za-z_][\w \t*]*?)\b(nslam_\w+)\s*\(([^()]*)\)\s*;"
+    for ret, name, params in re.findall(prototype, _header_text(), re.M):
+        args = []
+        for p in (() if params.strip() == "void" else params.split(",")):
+            text, _, array = re.fullmatch(r"\s*(.*?)(\w+)\s*(\[\w*\])?\s*", p, re.S).groups()
+            base, depth = ctype(text)
+            args.append((base, depth + (1 if array else 0)))
+        base, depth = ctype(ret)
+        protos.append((name, base + "*" * depth, args))
+    return protos
+
+
+_C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+              "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
+_C_POINTEES = dict(_C_SCALARS, int8_t=ctypes.c_int8, uint8_t=ctypes.c_uint8, int16_t=ctypes.c_int16,
+                   uint16_t=ctypes.c_uint16, uint32_t=ctypes.c_uint32)
+_C_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64, "char*": ctypes.c_char_p}
+
+
+def _signature_faults(protos, table, mirrors):
+    """Where table (name → (restype, argtypes)) departs from the prototypes → [(name, argument index or "restype" or
+    "count", what)].  A scalar must be the ctypes class of exactly its C type; a pointer may be c_void_p or POINTER
+    of its pointee's class; a struct pointer must be POINTER of the struct's mirror (mirrors: C name → class), a
+    pointer to pointer c_void_p or POINTER(c_void_p); restype is exact; no entry point is exempt."""
+    faults = []
+    for name, ret, args in protos:
+        if name not in table:
+            faults.append((name, "count", "not in the table"))
+            continue
+        restype, argtypes = table[name]
+        if restype is not _C_RETURNS.get(ret):
+            faults.append((name, "restype", f"{ret} bound as {restype}"))
+        if len(argtypes) != len(args):
+            faults.append((name, "count", f"{len(args)} parameters, {len(argtypes)} argtypes"))
+            continue
+        for i, ((base, depth), got) in enumerate(zip(args, argtypes)):
+            if depth == 0:
+                allowed = [_C_SCALARS.get(base)]
+            elif depth == 2:
+                allowed = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+            elif depth == 1 and base in mirrors:
+                allowed = [ctypes.POINTER(mirrors[base])]
+            elif depth == 1 and base in _C_POINTEES:
+                allowed = [ctypes.c_void_p, ctypes.POINTER(_C_POINTEES[base])]
+            else:
+                allowed = [ctypes.c_void_p] if (depth, base) == (1, "void") else []  # an unknown type matches nothing
+            if not any(got is a for a in allowed):
+                faults.append((name, i, f"{base}{'*' * depth} bound as {got}"))
+    return faults
+
+
+def test_signatures_match_header(pkg):
+    """restype and every argtype of _lib.SIGNATURES against the prototypes of include/nslam.h (_signature_faults has
+    the rule): all 91 entry points, none left out.  The same comparison then runs on a copy of the table with two
+    planted faults (a c_float for nslam_mesh_select's double threshold, argument 5 counted from 0; a c_int32 for
+    nslam_query_fwd's int64_t n_pts, argument 2) and must report exactly those, by name and index."""
+    lib = pkg._lib
+    mirrors = {cname: getattr(lib, py) for py, cnames in _C_STRUCTS.items() for cname in cnames}
+    protos = _header_prototypes()
+    names = [p[0] for p in protos]
+    assert len(set(names)) == len(names)
+    assert len(protos) == len(_header_symbols()) == len(lib.SIGNATURES) == 91
+    assert names == list(lib.SIGNATURES), "SIGNATURES is kept in the header's order"
+    faults = _signature_faults(protos, lib.SIGNATURES, mirrors)
+    print(f"{len(protos)} prototypes compared, {len(faults)} faults")
+    assert faults == []
+
+    planted = {n: (r, list(a)) for n, (r, a) in lib.SIGNATURES.items()}
+    assert planted["nslam_mesh_select"][1][5] is ctypes.c_double and planted["nslam_query_fwd"][1][2] is ctypes.c_int64
+    planted["nslam_mesh_select"][1][5] = ctypes.c_float
+    planted["nslam_query_fwd"][1][2] = ctypes.c_int32
+    caught = _signature_faults(protos, planted, mirrors)
+    print(f"planted faults caught: {caught}")
+    assert [(n, i) for n, i, _ in caught] == [("nslam_query_fwd", 2), ("nslam_mesh_select", 5)]
+
+
+# the enumerator families of nslam.h that the Python side uses: _lib.py mirrors each completely
+_C_FAMILIES = {"error code": r"NSLAM_(OK|E[A-Z]+)", "stage": r"NSLAM_STAGE_\w+", "decoder": r"NSLAM_DEC_\w+",
+               "loss mode": r"NSLAM_LOSS_\w+", "cull mode": r"NSLAM_CULL_\w+", "raster flag": r"NSLAM_RASTER_\w+",
+               "scene flag": r"NSLAM_SCENE_\w+"}
+
+
+def _mirror(lib, cname):
+    """The value _lib.py holds for the header's NSLAM_X: _lib.NSLAM_X or _lib.X, a stage in STAGES and a cull mode in
+    CULL_MODES under its lower-case name; None when _lib.py has none."""
+    short = cname[len("NSLAM_"):]
+    for prefix, table in (("STAGE_", lib.STAGES), ("CULL_", lib.CULL_MODES)):
+        if short.startswith(prefix):
+            return table.get(short[len(prefix):].lower())
+    return getattr(lib, cname, getattr(lib, short, None))
+
+
+def test_named_constants_match_header(pkg, tmp_path):
+    """Every `#define NSLAM_*` with a numeric value and every enumerator of include/nslam.h, printed by a gcc
+    probe: each one _lib.py mirrors is equal, the enumerator families the Python side uses are mirrored
+    completely, and the names the rest of the package re-exports are those values."""
+    lib, txt = pkg._lib, _header_text()
+    defines = [n for n, v in re.findall(r"^#define[ \t]+(NSLAM_\w+)[ \t]+(\S.*)$", txt, re.M)
+               if re.fullmatch(r"[\d\s()*+<-]+", v)]
+    enumerators = [item.split("=")[0].strip() for body in re.findall(r"\benum\b[^{;]*\{([^}]*)\}", txt)
+                   for item in body.split(",") if item.strip()]
+    assert {"NSLAM_EMB", "NSLAM_MAX_FRAMES", "NSLAM_ADAM_MAX_SEGS", "NSLAM_CAM_GRAD_WS_DOUBLES"} <= set(defines)
+    assert len(enumerators) == len(set(enumerators)) >= 20 and all(re.fullmatch(r"NSLAM_\w+", e) for e in enumerators)
+    out = _run_probe(tmp_path, [f'  printf("{n} %lld\\n", (long long)({n}));' for n in defines + enumerators])
+    value = {l.split()[0]: int(l.split()[1]) for l in out}
+    assert set(value) == set(defines + enumerators)
+
+    mirrored = {n: _mirror(lib, n) for n in value if _mirror(lib, n) is not None}
+    for n, v in mirrored.items():
+        assert v == value[n], (n, v, value[n])
+    assert {"NSLAM_EMB", "NSLAM_MAX_FRAMES", "NSLAM_ADAM_MAX_SEGS", "NSLAM_CAM_GRAD_WS_DOUBLES"} <= set(mirrored)
+    for family, pattern in _C_FAMILIES.items():
+        members = [n for n in enumerators if re.fullmatch(pattern, n)]
+        assert members and set(members) <= set(mirrored), (family, sorted(set(members) - set(mirrored)))
+    # the two dicts hold nothing the header lacks
+    assert len(lib.STAGES) == sum(n.startswith("NSLAM_STAGE_") for n in enumerators)
+    assert len(lib.CULL_MODES) == sum(n.startswith("NSLAM_CULL_") for n in enumerators)
+    # the public names elsewhere in the package are these values, not copies
+    ops = pkg.ops
+    assert ops.CAM_GRAD_WS_DOUBLES == value["NSLAM_CAM_GRAD_WS_DOUBLES"] and ops.CULL_MODES is lib.CULL_MODES
+    assert (ops.RASTER_CLEAR, ops.RASTER_SMALL, ops.RASTER_BIG, ops.RASTER_RESOLVE, ops.RASTER_ALL) == tuple(
+        value["NSLAM_RASTER_" + n] for n in ("CLEAR", "SMALL", "BIG", "RESOLVE", "ALL"))
+    assert (ops.SCENE_POINTS, ops.SCENE_ALL) == (value["NSLAM_SCENE_POINTS"], value["NSLAM_SCENE_ALL"])
+    assert pkg.packing.EMB == value["NSLAM_EMB"] and pkg.tsdf.MAX_FRAMES == lib.MAX_FRAMES == value["NSLAM_MAX_FRAMES"]
 
 
 def test_v4_entry_points_validate_without_gpu(pkg):
