@@ -43,6 +43,21 @@ def select_uv(i, j, n, depth, color, device="cuda:0", generator=None):
     return i[idx], j[idx], depth.reshape(-1)[idx], color.reshape(-1, 3)[idx]
 
 
+_SELECT_UV = select_uv  # the product's own pixel selection
+
+
+def device_draws(generator):
+    """Whether a fused loop may draw its pixels in the gather kernel: nobody pins the draws, neither by
+    replacing select_uv (tests do) nor by passing a generator."""
+    return select_uv is _SELECT_UV and generator is None
+
+
+def replays_graphs(owner):
+    """Whether this call of a Mapper / Tracker may replay cached hipGraphs: graphs on, device draws, and no
+    per-iteration hook (a hooked call runs eagerly, the hook before each iteration)."""
+    return bool(owner.graphs) and owner._iter_hook is None and device_draws(owner.generator)
+
+
 def get_sample_uv(H0, H1, W0, W1, n, depth, color, device="cuda:0", generator=None):
     """src/common.py:110-122."""
     depth = depth[H0:H1, W0:W1]

@@ -19,14 +19,17 @@ Differences from the reference (none changes the maths):
   * pixel draws: through common.select_uv (torch.randint, eager) when it is replaced (tests pin the
     draws that way) or a generator is given; otherwise drawn inside the gather kernel (uniform over
     the image like select_uv, a counter-based stream instead of torch's Philox) so that each stage's
-    iterations are captured ONCE in a hipGraph and replayed by every later call of the same shape
-    (the window's frames are copied into persistent slots, the frustum selection is bound on the
-    device with capacity-sized buffers: engine.MappingEngine.bind_masks).
+    iterations are captured ONCE in a hipGraph and replayed by every later call with the same plan
+    (StagePlan below: the graph's key holds every host value it baked in; ops.GraphCache; the window's
+    frames are copied into persistent slots, the frustum selection is bound on the device with
+    capacity-sized buffers: engine.MappingEngine.bind_masks).
 One pass of the mapping loop driver (Mapper.run, Mapper.py:572-654) is `map_frame`; NICE_SLAM.run schedules it
 serially (nice_slam.py).
 """
 from __future__ import annotations
 
+import collections
+import functools
 import os
 import time
 
@@ -38,8 +41,21 @@ from . import ops
 from .common import (get_camera_from_tensor, get_samples, get_tensor_from_camera, inside_mask, pose4,
                      random_select)
 
-_SELECT_UV = _common.select_uv  # the product's own pixel selection (a replacement one forces eager draws)
 _STAGE_GROUPS = ("decoders", "coarse", "middle", "fine", "color")
+
+# The plans of a fused call: each is the key of a cached graph (ops.GraphCache) and holds every host value the
+# captured body reads; the eager path walks the same records.
+# StagePlan: `iters` iterations of one stage over a window of F frames × n_per pixels whose slots c0.. hold the
+# ncam BA cameras.  lrs: the effective rates of _STAGE_GROUPS (cfg × lr_factor); cam_lr: the cameras' (0 before
+# the colour stage and without BA); trainable: the decoders in the optimiser; record: losses are kept; first:
+# the run also sets the BA cameras up; prefetch: the next batch is drawn beside this iteration;
+# intrinsics = (fx, fy, cx, cy); seed: the device draws' stream.
+StagePlan = collections.namedtuple("StagePlan", "kind stage iters F n_per c0 ncam lrs cam_lr trainable record first "
+                                                "prefetch H W intrinsics seed")
+# SetupPlan: the per-call setup over n_kf scored keyframes; frustum / coarse / hooked (get_mask_from_c2w is
+# replaced on the instance) steer how the frustum selection is bound (_bind_frustum); trainable names the
+# optimiser whose state the setup zeroes.
+SetupPlan = collections.namedtuple("SetupPlan", "kind n_kf frustum coarse hooked trainable H W intrinsics")
 
 
 def _remap_bilinear(img, u, v):
@@ -257,11 +273,11 @@ class Mapper(object):
         self.fused = True   # optimize_map on engine.MappingEngine (False: the autograd drop-in)
         self.graphs = True  # fused path with device draws: each stage's iterations as one cached hipGraph
         self._eng = None
-        self._fopt = None
+        self._fopt = {}     # trainable decoders -> the fused path's FusedAdam
         self._cam = {}      # number of BA cameras -> (cams, grad, ws, tickets, FusedAdam)
         self._slots = None  # (depth [F,H,W], color [F,H,W,3], c2w [F,4,4]) of the window
         self._setup = None  # persistent inputs of the captured per-call setup (_setup_inputs)
-        self._graphs = {}
+        self._graphs = ops.GraphCache()  # StagePlan / SetupPlan -> (graph, what its body returned)
         # the device draws' stream key (from torch's CPU generator, so torch.manual_seed pins it)
         self._draw_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         self.calls = 0
@@ -284,10 +300,11 @@ class Mapper(object):
         # mask.sum() / uv.shape[0] as the reference divides: an integer count over the sample count
         return [int(cnt) / n for cnt in counts.cpu()]
 
-    def _overlap_counts(self, gt_color, gt_depth, c2w, poses, N_samples=16, pixels=100):
-        """The device half of keyframe_overlap_scores: (counts [len(poses)] device int64 or None, samples)."""
+    def _overlap_counts(self, gt_color, gt_depth, c2w, poses, N_samples=16, pixels=100, camera=None):
+        """The device half of keyframe_overlap_scores: (counts [len(poses)] device int64 or None, samples).
+        camera = (H, W, fx, fy, cx, cy), the mapper's own by default (the captured setup passes its plan's)."""
         dev = self.device
-        H, W, fx, fy, cx, cy = self.H, self.W, self.fx, self.fy, self.cx, self.cy
+        H, W, fx, fy, cx, cy = camera or (self.H, self.W, self.fx, self.fy, self.cx, self.cy)
         rays_o, rays_d, gd, _ = get_samples(0, H, 0, W, pixels, H, W, fx, fy, cx, cy, c2w, gt_depth, gt_color, dev,
                                             generator=self.generator)
         if not poses:
@@ -397,11 +414,12 @@ class Mapper(object):
         """Decoders in the optimiser's "decoders" group (Mapper.py:335-341)."""
         return tuple(n for n, fixed in (("fine", self.fix_fine), ("color", self.fix_color)) if not fixed)
 
-    def _optimizer(self, eng):
-        """The persistent FusedAdam of the fused path: groups decoders / coarse / middle / fine / colour as
+    def _optimizer(self, eng, trainable):
+        """The persistent FusedAdam of the fused path, one per set of trainable decoders (graphs hold its
+        state by address, and their keys name that set): groups decoders / coarse / middle / fine / colour as
         the reference's (Mapper.py:365-389); grid groups hold the frustum rows with their live count."""
-        if self._fopt is None:
-            dec = [eng.decs[n].param for n in self._trainable() if n in eng.decs]
+        if trainable not in self._fopt:
+            dec = [eng.decs[n].param for n in trainable if n in eng.decs]
             groups = [{"params": dec, "lr": 0.0}]
             for name in _STAGE_GROUPS[1:]:
                 k = "grid_" + name
@@ -410,8 +428,8 @@ class Mapper(object):
                     groups.append({"params": [eng.c[k]], "lr": 0.0, "rows": rows, "n_live": n_live})
                 else:
                     groups.append({"params": [], "lr": 0.0})
-            self._fopt = ops.FusedAdam(groups)
-        return self._fopt
+            self._fopt[trainable] = ops.FusedAdam(groups)
+        return self._fopt[trainable]
 
     def _cam_state(self, n):
         """Persistent BA camera buffers for n cameras: cams [n,7], their gradient, the camera-gradient
@@ -432,25 +450,30 @@ class Mapper(object):
             self._slots = (torch.zeros(n, H, W, dtype=torch.float32, device=dev),
                            torch.zeros(n, H, W, 3, dtype=torch.float32, device=dev),
                            torch.eye(4, dtype=torch.float32, device=dev).repeat(n, 1, 1))
-            self._graphs.clear()  # (captured against the old slots)
+            self._graphs.drop("stage")  # the window slots regrew: the stage graphs read the old ones
         return self._slots
 
-    def _bind_frustum(self, eng, c2w, depth):
+    def _setup_plan(self, n_kf=0):
+        """This call's per-call setup as a SetupPlan (n_kf: the keyframes its overlap selection scores)."""
+        return SetupPlan("setup", int(n_kf), bool(self.frustum_feature_selection), bool(self.coarse_mapper),
+                         "get_mask_from_c2w" in self.__dict__, self._trainable(), int(self.H), int(self.W),
+                         (float(self.fx), float(self.fy), float(self.cx), float(self.cy)))
+
+    def _bind_frustum(self, eng, c2w, depth, plan):
         """This call's frustum selection bound into the engine's capacity buffers (Mapper.py:314-333): the
         fused kernel (nslam_frustum_rows) per grid shape, the other grids of that shape copying its rows;
         the coarse grid (an all-true mask, Mapper.py:113-115) and frustum_feature_selection=False through
-        bind_masks.  get_mask_from_c2w replaced on the instance (a test hook) also goes through bind_masks."""
-        keys = self._grid_keys()
-        if (not self.frustum_feature_selection or self.coarse_mapper
-                or "get_mask_from_c2w" in self.__dict__):
-            eng.bind_masks(self._call_masks(c2w, depth))
+        bind_masks.  get_mask_from_c2w replaced on the instance (a test hook) also goes through bind_masks.
+        Which of these, and the camera, come from the SetupPlan; the grids are the engine's."""
+        if not plan.frustum or plan.coarse or plan.hooked:
+            eng.bind_masks(self._call_masks(eng, c2w, depth, plan))
             return
-        if getattr(eng, "_cap_keys", None) != tuple(sorted(keys)):
-            eng.bind_masks({k: None for k in keys})  # (first call: the capacity buffers)
+        if getattr(eng, "_cap_keys", None) != tuple(sorted(eng.c)):
+            eng.bind_masks({k: None for k in eng.c})  # (first call: the capacity buffers)
         eng.rows_gen += 1  # the slot maps are rewritten in place: live-point lists formed from them are stale
         done = {}
-        for k in keys:
-            shp = tuple(self.c[k].shape[2:])
+        for k, grid in eng.c.items():
+            shp = tuple(grid.shape[2:])
             rows, n_live = eng.live_rows(k)
             slot = eng.slot[k]
             if shp in done:
@@ -459,22 +482,28 @@ class Mapper(object):
                 rows.copy_(r0)
                 n_live.copy_(n0)
             else:
-                frustum_rows_device(c2w, shp, depth, self.bound, self.H, self.W, self.fx, self.fy, self.cx, self.cy,
-                                    slot, rows, n_live)
+                frustum_rows_device(c2w, shp, depth, self.bound, plan.H, plan.W, *plan.intrinsics, slot, rows, n_live)
                 done[shp] = (slot, rows, n_live)
 
-    def _call_masks(self, c2w, depth):
-        """This call's frustum masks (Mapper.py:314-333; None = every voxel): grids of one shape share one."""
+    def _call_masks(self, eng, c2w, depth, plan):
+        """This call's frustum masks of the engine's grids (Mapper.py:314-333; None = every voxel, all of them
+        without plan.frustum): grids of one shape share one.  A hooked get_mask_from_c2w is called; otherwise
+        frustum_mask with the plan's camera."""
+        def mask(k, shp):
+            if plan.hooked:
+                return self.get_mask_from_c2w(c2w, k, shp, depth)
+            return frustum_mask(c2w, k, shp, depth, self.bound, plan.H, plan.W, *plan.intrinsics)
+
         masks, by_shape = {}, {}
-        for k in self._grid_keys():
-            shp = tuple(self.c[k].shape[2:])
-            if not self.frustum_feature_selection:
+        for k, grid in eng.c.items():
+            shp = tuple(grid.shape[2:])
+            if not plan.frustum:
                 masks[k] = None
             elif k == "grid_coarse":
-                masks[k] = self.get_mask_from_c2w(c2w, k, shp, depth)
+                masks[k] = mask(k, shp)
             else:
                 if shp not in by_shape:
-                    by_shape[shp] = self.get_mask_from_c2w(c2w, k, shp, depth)
+                    by_shape[shp] = mask(k, shp)
                 masks[k] = by_shape[shp]
         return masks
 
@@ -487,7 +516,7 @@ class Mapper(object):
                                 "color": torch.zeros(H, W, 3, dtype=torch.float32, device=dev),
                                 "c2w": torch.eye(4, dtype=torch.float32, device=dev),
                                 "poses": torch.eye(4, dtype=torch.float32, device=dev).repeat(max(8, 2 * K), 1, 1)}
-            self._graphs = {k: v for k, v in self._graphs.items() if k[0] != "setup"}  # (bound to the old buffers)
+            self._graphs.drop("setup")  # the setup's input buffers were (re)made: its graphs read the old ones
         return st
 
     # -- optimize_map on the fused engine (see the module docstring) -------------------------------
@@ -499,100 +528,129 @@ class Mapper(object):
             tm["ev"][name] = torch.cuda.Event(enable_timing=True)
             tm["ev"][name].record()
 
+    def _run_setup(self, plan, eng, st):
+        """The captured per-call setup of `plan` over the inputs st (_setup_inputs): the frustum selection, a
+        fresh Adam (its state made, then zeroed) and the overlap counts of the plan's keyframes →
+        (counts or None, samples)."""
+        self._bind_frustum(eng, st["c2w"], st["depth"], plan)
+        opt = self._optimizer(eng, plan.trainable)
+        opt.init_state()
+        opt.reset_state()
+        if plan.n_kf:
+            return self._overlap_counts(st["color"], st["depth"], st["c2w"], [st["poses"][i] for i in range(plan.n_kf)],
+                                        camera=(plan.H, plan.W) + plan.intrinsics)
+        return None, 0
+
     def _fused_setup(self, eng, use_graphs, overlap_here, cur_gt_color, cur_gt_depth, cur_c2w, keyframe_dict):
         """What a call enqueues before its keyframe selection: the frustum selection (Mapper.py:314-333) bound
         on the device, a fresh Adam (Mapper.py:365-389: zero moments and step counts) and, when overlap_here,
-        the overlap counts of keyframe_dict[:-1] — with graphs as one captured graph per keyframe count over
+        the overlap counts of keyframe_dict[:-1] — with graphs as one captured graph per SetupPlan over
         persistent inputs.  Returns (optimiser, counts, samples)."""
+        kfs = keyframe_dict[:-1] if overlap_here else []  # (overlap_here: only with graphs)
+        plan = self._setup_plan(len(kfs))
         if not use_graphs:
-            self._bind_frustum(eng, cur_c2w, cur_gt_depth)
-            opt = self._optimizer(eng)
+            self._bind_frustum(eng, cur_c2w, cur_gt_depth, plan)
+            opt = self._optimizer(eng, plan.trainable)
             opt.reset_state()
             return opt, None, 0
-        dev = self.device
-        kfs = keyframe_dict[:-1] if overlap_here else []
-        st = self._setup_inputs(len(kfs))
+        st = self._setup_inputs(plan.n_kf)
         st["depth"].copy_(cur_gt_depth)
         st["color"].copy_(cur_gt_color)
         st["c2w"][:cur_c2w.shape[0]].copy_(cur_c2w)
         if kfs:
-            st["poses"][:len(kfs)].copy_(torch.stack([kf["est_c2w"].to(dev).float()[:4] for kf in kfs]))
-
-        def setup():
-            self._bind_frustum(eng, st["c2w"], st["depth"])
-            o = self._optimizer(eng)
-            o.init_state()
-            o.reset_state()
-            if kfs:
-                return self._overlap_counts(st["color"], st["depth"], st["c2w"],
-                                            [st["poses"][i] for i in range(len(kfs))])
-            return None, 0
-
-        key = ("setup", len(kfs))
-        if key not in self._graphs:
-            setup()  # eager warm-up: first-time allocations (engine capacity buffers, Adam state, caches)
-            g = torch.cuda.CUDAGraph()
-            with ops.capture(g):
-                out = setup()
-            self._graphs[key] = (g, out)
-        g, (counts, n_samp) = self._graphs[key]
+            st["poses"][:len(kfs)].copy_(torch.stack([kf["est_c2w"].to(self.device).float()[:4] for kf in kfs]))
+        # (the warm-up is the setup itself: the engine's capacity buffers, the Adam state and torch's caches)
+        g, (counts, n_samp), _ = self._graphs.graph(plan, body=lambda: self._run_setup(plan, eng, st),
+                                                    warm=lambda: self._run_setup(plan, eng, st))
         g.replay()
-        return self._optimizer(eng), counts, n_samp
+        return self._optimizer(eng, plan.trainable), counts, n_samp
 
-    def _fused_iteration(self, eng, opt, win, stage, record=None):
-        """One mapping iteration on the engine over the window `win`; record(ray_loss) when given."""
-        H, W, n_per = self.H, self.W, win.n_per
+    def _stage_plans(self, num_joint_iters, lr_factor, win):
+        """A call's schedule over the window `win` as StagePlans, one per run of a stage (Mapper.py:403-421)."""
+        rates = self.cfg["mapping"]["stage"]
+        trainable, record = self._trainable(), self.loss_history is not None
+        camera = (int(self.H), int(self.W), (float(self.fx), float(self.fy), float(self.cx), float(self.cy)))
+        plans = []
+        for stage, iters in self._stage_runs(num_joint_iters):
+            # device draws: the next iteration's gather + sampler run beside this one's render and backward
+            # (engine prefetch); every run of one stage starts with its own batch (eng.drop_prefetch), so a
+            # captured run holds its whole prefetch chain.  With BA the poses the rays come from move only in
+            # the colour stage (the cameras' lr is 0 before it, Mapper.py:420-421: their Adam state advances,
+            # the 7-vectors do not), so only colour-stage BA iterations draw their rays serially.
+            prefetch = win.ar is None and (not win.ncam or stage != "color")
+            plans.append(StagePlan(
+                "stage", stage, iters, win.F, win.n_per, win.c0, win.ncam,
+                tuple(rates[stage][name + "_lr"] * lr_factor for name in _STAGE_GROUPS),
+                float(self.BA_cam_lr) if (win.ncam and stage == "color") else 0.0,
+                trainable, record, not plans and win.ncam > 0, prefetch, *camera, int(self._draw_seed)))
+        return plans
+
+    @staticmethod
+    def _set_stage_lr(plan, opt, win, zero=False):
+        """The run's learning rates (Mapper.py:413-421), or all zero."""
+        for group, lr in zip(opt.param_groups, plan.lrs):
+            group["lr"] = 0.0 if zero else lr
+        if plan.ncam:
+            win.copt.param_groups[0]["lr"] = 0.0 if zero else plan.cam_lr
+
+    @staticmethod
+    def _fused_iteration(plan, eng, opt, win, record=None, generator=None):
+        """One mapping iteration of `plan` on the engine over the window `win`; record(ray_loss) when given.
+        generator: of the select_uv draws (a window with eager draws, win.ar)."""
+        n_per = plan.n_per
         pix = None
         if win.ar is not None:  # select_uv per frame, in optimize_frame order (Mapper.py:437-467)
             ar = win.ar
-            pix = torch.empty(win.F * n_per, dtype=torch.int64, device=self.device)
+            pix = torch.empty(plan.F * n_per, dtype=torch.int64, device=ar.device)
             for fr in win.optimize_frame:
                 s = win.order.index(fr)
                 pix[s * n_per:(s + 1) * n_per] = _common.select_uv(ar, ar, n_per, ar, ar.view(-1, 1).expand(-1, 3),
-                                                                   device=self.device, generator=self.generator)[0]
-        # device draws: the next iteration's gather + sampler run beside this one's render and backward
-        # (engine prefetch); every run of one stage starts with its own batch (eng.drop_prefetch), so a
-        # captured run holds its whole prefetch chain.  With BA the poses the rays come from move only in
-        # the colour stage (the cameras' lr is 0 before it, Mapper.py:420-421: their Adam state advances,
-        # the 7-vectors do not), so only colour-stage BA iterations draw their rays serially.
-        prefetch = win.ar is None and (not win.ncam or stage != "color")
-        ray_loss, _ = eng.iteration(stage, win.frames, pix, n_per, (H, W), (self.fx, self.fy, self.cx, self.cy), opt,
-                                    trainable_decoders=self._trainable(), use_gt_in_sampler=not self.coarse_mapper,
-                                    seed=self._draw_seed, post_bwd=win.post_bwd if win.ncam else None,
-                                    prefetch=prefetch)
+                                                                   device=ar.device, generator=generator)[0]
+        ray_loss, _ = eng.iteration(plan.stage, win.frames, pix, n_per, (plan.H, plan.W), plan.intrinsics, opt,
+                                    trainable_decoders=plan.trainable, use_gt_in_sampler=plan.stage != "coarse",
+                                    seed=plan.seed, post_bwd=win.post_bwd if plan.ncam else None,
+                                    prefetch=plan.prefetch)
         if record is not None:
             record(ray_loss)
 
-    def _set_stage_lr(self, opt, win, stage, lr_factor, zero=False):
-        """The stage's learning rates (Mapper.py:413-421), or all zero."""
-        st = self.cfg["mapping"]["stage"][stage]
-        for gi, name in enumerate(_STAGE_GROUPS):
-            opt.param_groups[gi]["lr"] = 0.0 if zero else st[name + "_lr"] * lr_factor
-        if win.ncam:
-            win.copt.param_groups[0]["lr"] = self.BA_cam_lr if (stage == "color" and not zero) else 0.0
-
-    def _capture_stage(self, eng, opt, win, stage, n, lr_factor, first):
-        """n iterations of one stage as a hipGraph → (graph, its losses or None).  Before it one zero-lr eager
-        iteration (the maps do not move; lazily made streams, events, tickets and draw counters exist before
-        capture); the capture itself runs nothing.  first: the graph also sets the BA cameras up."""
-        if win.ncam:
+    @staticmethod
+    def _run_stage(plan, eng, opt, win, record=None, hook=None, generator=None):
+        """The run `plan`, as the eager path executes and a stage graph captures it: its rates, its own first
+        batch, the BA cameras' set-up when it is the call's first run, then the iterations — hook(i) before
+        and record(i, ray_loss) after the i-th.  Every host value comes from the plan."""
+        Mapper._set_stage_lr(plan, opt, win)
+        eng.drop_prefetch()
+        if plan.first:
             win.cams_init()
-        self._set_stage_lr(opt, win, stage, lr_factor, zero=True)
-        eng.drop_prefetch()
-        self._fused_iteration(eng, opt, win, stage)
-        self._set_stage_lr(opt, win, stage, lr_factor)
+        for i in range(plan.iters):
+            if hook is not None:
+                hook(i)
+            Mapper._fused_iteration(plan, eng, opt, win, None if record is None else functools.partial(record, i),
+                                    generator)
+
+    def _stage_graph(self, plan, eng, opt, win):
+        """The run `plan` as a cached hipGraph → (graph, its losses [iters] or None, captured now).  Its
+        warm-up is one zero-lr eager iteration: the maps do not move, but the Adam state advances and BA
+        rewrites the slots' poses, which the caller resets after a capture."""
+        draws = eng.draws(plan.seed)
         losses = None
-        if self.loss_history is not None:
-            losses = torch.zeros(n, dtype=torch.float64, device=self.device)
-        g = torch.cuda.CUDAGraph()
-        eng.drop_prefetch()
-        with ops.capture(g):
-            if first:
+
+        def warm():
+            nonlocal losses
+            if plan.ncam:
                 win.cams_init()
-            for i in range(n):
-                self._fused_iteration(eng, opt, win, stage,
-                                      None if losses is None else (lambda rl, i=i: losses[i].copy_(rl.sum())))
-        return g, losses
+            self._set_stage_lr(plan, opt, win, zero=True)
+            eng.drop_prefetch()
+            self._fused_iteration(plan, eng, opt, win)
+            if plan.record:  # (made before the capture: not from the graph's pool, no fill in the graph)
+                losses = torch.zeros(plan.iters, dtype=torch.float64, device=eng.device)
+
+        def body():
+            self._run_stage(plan, eng, opt, win, None if losses is None else (lambda i, rl: losses[i].copy_(rl.sum())))
+            return losses, draws  # (draws: kept with the graph that advances it, ops.GraphCache)
+
+        g, (losses, _), captured = self._graphs.graph(plan, body, warm, rewind=[draws.counter])
+        return g, losses, captured
 
     def _optimize_map_fused(self, num_joint_iters, lr_factor, idx, cur_gt_color, cur_gt_depth, gt_cur_c2w,
                             keyframe_dict, keyframe_list, cur_c2w):
@@ -605,8 +663,8 @@ class Mapper(object):
         eng = self.engine()
         for d in eng.decs.values():  # parameters may have been assigned since the last call
             d.repack()
-        device_draws = _common.select_uv is _SELECT_UV and self.generator is None
-        use_graphs = self.graphs and device_draws and self._iter_hook is None  # (a hooked call runs eagerly)
+        device_draws = _common.device_draws(self.generator)
+        use_graphs = _common.replays_graphs(self)
         # 1. Everything that does not depend on the keyframe selection is enqueued first: the selection reads
         # its overlap scores back to the host (the reference's numpy ranking), and what is queued before
         # that read overlaps the previous call's iterations still running on the device.
@@ -626,49 +684,30 @@ class Mapper(object):
         # 3. its frames in the persistent slots, and the BA cameras
         win = _Window(self, optimize_frame, oldest_frame, keyframe_dict, cur_gt_depth, cur_gt_color, cur_c2w,
                       device_draws)
-        # 4. the schedule; 5. with graphs, each run's graph (cached by everything it was captured for)
-        runs = self._stage_runs(num_joint_iters)
+        # 4. the schedule: one plan per stage run; 5. with graphs, each plan's graph
+        plans = self._stage_plans(num_joint_iters, lr_factor, win)
         hist = self.loss_history
         if use_graphs:
-            # the warm-up iterations of a capture draw pixels too: the draw stream is rewound afterwards, so a
-            # call draws the same pixels whether its graphs were cached or just captured (and as the eager path)
-            ctr = eng.draws(self._draw_seed).counter
-            ctr0 = ctr.clone()
-            plan, warmed = [], False
-            for ri, (stg, n) in enumerate(runs):
-                first = ri == 0 and win.ncam > 0
-                key = ("stage", stg, n, win.F, win.n_per, win.c0, win.ncam, float(lr_factor), hist is not None,
-                       self._trainable(), first)
-                if key not in self._graphs:
-                    self._graphs[key] = self._capture_stage(eng, opt, win, stg, n, lr_factor, first)
-                    warmed = True
-                plan.append((stg, self._graphs[key]))
-            ctr.copy_(ctr0)
-            if warmed:  # (the warm-up steps moved the Adam state and rewrote the BA cameras' poses)
+            graphs = [self._stage_graph(plan, eng, opt, win) for plan in plans]
+            if any(captured for _, _, captured in graphs):  # (what the warm-up iterations moved)
                 opt.reset_state()
                 win.restore_poses()
         self._mark(tm, "window")
         # 6. the iterations: replayed, or eagerly with the hook before each (Mapper.py:426-428)
         if use_graphs:
-            for stg, (g, losses) in plan:
-                self.stage = stg
+            for plan, (g, losses, _) in zip(plans, graphs):
+                self.stage = plan.stage
                 g.replay()
                 if hist is not None:
                     hist.extend(losses.clone().unbind())
         else:
-            if win.ncam:
-                win.cams_init()
-            joint_iter = 0
-            for stg, n in runs:
-                self.stage = stg
-                self._set_stage_lr(opt, win, stg, lr_factor)
-                eng.drop_prefetch()
-                for _ in range(n):
-                    if self._iter_hook is not None:
-                        self._iter_hook(joint_iter)
-                    joint_iter += 1
-                    self._fused_iteration(eng, opt, win, stg,
-                                          None if hist is None else (lambda rl: hist.append(rl.sum())))
+            done = 0
+            for plan in plans:
+                self.stage = plan.stage
+                hook = self._iter_hook
+                self._run_stage(plan, eng, opt, win, None if hist is None else (lambda i, rl: hist.append(rl.sum())),
+                                None if hook is None else (lambda i, done=done: hook(done + i)), self.generator)
+                done += plan.iters
         self._mark(tm, "iterations")
         if tm is not None:
             self.timing.append(tm)
@@ -914,10 +953,8 @@ class Mapper(object):
         """One pass of Mapper.run's loop body (Mapper.py:572-654) for frame idx; True when it was the last.
 
         The colour-refinement pass mutates the live Mapper as the reference does (window ×2, both ratios 0,
-        fix_color, frustum selection off).  The stage graphs' keys cover the window, the schedule and the
-        trainable decoders, and the window slots regrow by size; the cached optimiser (its decoder group was
-        built with the colour decoder in it) and the captured per-call setup (it captured the frustum kernel) do
-        not see the change, so both are dropped there, with the graphs bound to them.
+        fix_color, frustum selection off).  Every one of these is in the plans that key the graphs and the
+        optimiser, so the pass gets graphs and an optimiser of its own; the window slots regrow by size.
 
         On a frame whose mapping visualisation fires, optimize_map runs its eager fused path with the visualiser
         called before every iteration, where Mapper.py:426-428 has it; the first frame's one-off schedule
@@ -941,8 +978,6 @@ class Mapper(object):
                 num_joint_iters *= 5
                 self.fix_color = True
                 self.frustum_feature_selection = False
-                self._fopt = None
-                self._graphs.clear()
             else:
                 outer_joint_iters = 1 if self.nice else 3
         else:

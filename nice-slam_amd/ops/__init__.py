@@ -21,6 +21,8 @@ public name re-exported here (callers write ops.<name>).  No CPU fallback.
 
 Two switches live here and are assigned from outside (ops.TIMER by the bench, ops.SPLIT_FWD by tests): the
 submodules read them from this package at call time, through span() and in query_fwd_launch.
+The two helpers of hipGraph capture live here too: capture() and GraphCache, the cache the Mapper and the
+Tracker keep their graphs in.
 """
 import contextlib
 import gc
@@ -89,6 +91,57 @@ def capture(graph):
     finally:
         if enabled:
             gc.enable()
+
+
+class GraphCache(dict):
+    """The captured hipGraphs of one owner: plan record -> (graph, what its captured body returned).
+
+    A key is a small frozen record (a namedtuple) whose first field `kind` names what was captured and whose
+    other fields are every host value that capture baked into kernel arguments: learning rates, counts,
+    image sizes, the draw seed.  The captured body takes the record and reads its host values from nowhere
+    else, so a value cannot be baked unless it is in the key; a changed setting is a new key and a new graph,
+    never a replay of the old value.  What an engine froze at its construction (sample counts, w_color, the
+    tracker's edges) is not in the key: it belongs to the engine's identity, and whoever replaces an engine or
+    a buffer that graphs hold by address drops them (drop()).
+
+    graph(key, body, warm, rewind) is the one capture sequence:
+      1. `rewind` tensors are cloned.  The draw counter is the usual one: the warm-up draws pixels too, and
+         rewinding it makes a call draw the same pixels whether its graph was cached or just captured, and
+         the same as the eager path.
+      2. warm() runs eagerly.  It is the body with zero learning rates (the maps do not move), so that
+         everything made lazily exists before the capture: streams, events, Adam state and tickets, draw
+         counters, capacity buffers.  Made during a capture they would come from the graph's private pool
+         with their initialisation baked into every replay.
+      3. body() is captured under ops.capture (the garbage collector off: see there).  Capturing runs nothing.
+      4. the `rewind` tensors are restored and (graph, body's return value) is stored.
+    What the warm-up moved that is not a snapshot (the Adam moments it advanced, poses it rewrote) the caller
+    resets when `captured` comes back true.
+
+    A graph holds device memory by address, so whatever it reads or writes must outlive it.  Persistent buffers
+    belong to the owner; a body returns what nobody else keeps.  The draw state is the case in point: an engine
+    caches the PixelDraws of one seed only (MappingEngine.draws), so after a change of seed nothing else would
+    hold the counter that the old seed's graph still advances.  Bodies that draw return their PixelDraws, and
+    the entry keeps it alive as long as the graph."""
+
+    def graph(self, key, body, warm=None, rewind=()):
+        """(graph, body's return value, whether it was captured by this call) of `key`; a hit runs nothing."""
+        if key in self:
+            return self[key] + (False,)
+        saved = [t.clone() for t in rewind]
+        if warm is not None:
+            warm()
+        g = torch.cuda.CUDAGraph()
+        with capture(g):
+            out = body()
+        for t, s in zip(rewind, saved):
+            t.copy_(s)
+        self[key] = (g, out)
+        return g, out, True
+
+    def drop(self, kind=None):
+        """Forget the graphs of one kind (all of them: None)."""
+        for key in [k for k in self if kind is None or k.kind == kind]:
+            del self[key]
 
 
 SPLIT_FWD = True  # decoder-parallel forward (nslam_query_fwd_ws); False: one wave runs every decoder

@@ -14,6 +14,7 @@ its pixels in the gather kernel, as every other fused tracker does; `fused = Fal
 """
 from __future__ import annotations
 
+import collections
 import copy
 
 import numpy as np
@@ -24,7 +25,9 @@ from . import ops
 from .common import (camera_tensors, constant_speed_guess, get_camera_from_tensor, get_samples,
                      get_tensor_from_camera, inside_mask, pose4)
 
-_SELECT_UV = _common.select_uv
+# A frame's captured camera loop: the key of its graph (ops.GraphCache) and every host value its body reads.
+# cam_lr / lr_quat: the Adam rates (lr_quat None without seperate_LR); seed: the device draws' stream.
+FramePlan = collections.namedtuple("FramePlan", "kind iters n speed seperate_LR cam_lr lr_quat seed")
 
 
 class Tracker(object):
@@ -65,7 +68,7 @@ class Tracker(object):
         self.graphs = True    # fused, no generator: a frame's camera loop is one cached hipGraph (device draws)
         self._engine = None
         self._fstate = None   # persistent buffers of the captured camera loop
-        self._graphs = {}
+        self._graphs = ops.GraphCache()  # FramePlan -> the frame's graph
         self._draw_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         if not self.nice:  # iMAP*: the autograd camera loop (the fused engine evaluates the NICE decoders)
             self.fused = False
@@ -130,7 +133,7 @@ class Tracker(object):
                     self.c[key] = val.detach().clone().to(self.device)
                 self._engine = None  # re-bound to the new snapshot on first use
                 self._fstate = None
-                self._graphs.clear()
+                self._graphs.drop()  # (captured over the old snapshot's engine and buffers)
             self.prev_mapping_idx = self.mapping_idx[0].clone()
 
     def engine(self):
@@ -153,8 +156,7 @@ class Tracker(object):
         gt_depth, gt_color = gt_depth.to(device), gt_color.to(device)
         if idx == 0 or self.gt_camera:
             return gt_c2w.clone()
-        if (self.fused and self.graphs and self.generator is None and _common.select_uv is _SELECT_UV
-                and self._iter_hook is None):
+        if self.fused and _common.replays_graphs(self):
             return self._track_graph(gt_color, gt_depth, pre_c2w,
                                      prev2_c2w if self.const_speed_assumption else None)
         if self.const_speed_assumption and prev2_c2w is not None:
@@ -249,90 +251,96 @@ class Tracker(object):
 
     _iter_hook = None  # track(): called as hook(cam_iter, camera_tensor) before each camera iteration
 
-    def _lr2(self):
+    def _frame_plan(self, speed=False):
+        """This frame's camera loop as a FramePlan: the key of its graph and all its body reads."""
+        lr = float(self.cam_lr)
+        return FramePlan("frame", int(self.num_cam_iters), int(self.tracking_pixels), bool(speed),
+                         bool(self.seperate_LR), lr, lr * 0.2 if self.seperate_LR else None, int(self._draw_seed))
+
+    @staticmethod
+    def _lr2(plan, zero=False):
         """iteration()'s keywords for tracking.seperate_LR (Tracker.py:202-209, 226-227): the quaternion's
         Adam group steps with lr·0.2, and the candidate kept is the camera before the step."""
-        return {"lr_quat": self.cam_lr * 0.2, "best_before_step": True} if self.seperate_LR else {}
+        return {"lr_quat": 0.0 if zero else plan.lr_quat, "best_before_step": True} if plan.seperate_LR else {}
 
     def _track_fused(self, camera_tensor, gt_color, gt_depth):
-        """The camera loop of track_frame (Tracker.py:225-250) on the TrackingEngine: the best pose
+        """The camera loop of track_frame (Tracker.py:225-250) on the TrackingEngine, eagerly: the best pose
         (lowest pre-step loss → the pose right after that step, as the reference keeps it; with
         seperate_LR the pose before it, as the reference keeps it there) is selected on the device; no
-        host sync.  Without a generator the pixels are drawn in the gather
-        kernel and the whole loop is ONE hipGraph, captured on the first frame and replayed on every
-        later one (the frame is copied into persistent slots; a fresh Adam per frame by resetting its
-        state).  With a generator (pinned draws): torch.randint per iteration, eager."""
+        host sync.  Pixels by torch.randint per iteration (a generator pins them).  It walks the same
+        FramePlan as the captured loop (_track_graph)."""
         eng = self.engine()
         device = self.device
+        plan = self._frame_plan()
         cam = camera_tensor.detach().clone().requires_grad_(True)
-        opt = ops.FusedAdam([{"params": [cam], "lr": self.cam_lr}])
+        opt = ops.FusedAdam([{"params": [cam], "lr": plan.cam_lr}])
         best = cam.detach().clone()
         best_loss = torch.full((), float("inf"), dtype=torch.float64, device=device)
         depth = gt_depth.float().contiguous()
         color = gt_color.float().contiguous()
-        for cam_iter in range(self.num_cam_iters):
+        for cam_iter in range(plan.iters):
             if self._iter_hook is not None:
                 self._iter_hook(cam_iter, cam.detach())
-            pix = torch.randint(eng.n_window(), (self.tracking_pixels,), device=device, generator=self.generator)
-            eng.iteration(cam, depth, color, pix, opt, best=(best_loss, best), **self._lr2())  # (+ Tracker.py:245-247)
+            pix = torch.randint(eng.n_window(), (plan.n,), device=device, generator=self.generator)
+            eng.iteration(cam, depth, color, pix, opt, best=(best_loss, best), **self._lr2(plan))  # (+ Tracker.py:245-247)
         return pose4(get_camera_from_tensor(best))
+
+    def _frame_state(self):
+        """Persistent buffers of the captured camera loop (its graphs hold them by address)."""
+        if self._fstate is None:
+            dev = self.device
+            cam = torch.zeros(7, dtype=torch.float32, device=dev).requires_grad_(True)
+            self._fstate = {
+                "depth": torch.zeros(self.H, self.W, dtype=torch.float32, device=dev),
+                "color": torch.zeros(self.H, self.W, 3, dtype=torch.float32, device=dev),
+                "pre": torch.eye(4, dtype=torch.float32, device=dev), "prev2": torch.eye(4, dtype=torch.float32, device=dev),
+                "cam": cam, "opt": ops.FusedAdam([{"params": [cam], "lr": 0.0}]),
+                "best": torch.zeros(7, dtype=torch.float32, device=dev),
+                "best_loss": torch.zeros((), dtype=torch.float64, device=dev),
+                "out": torch.eye(4, dtype=torch.float32, device=dev)}
+            self._fstate["opt"].init_state()
+        return self._fstate
+
+    @staticmethod
+    def _frame(plan, eng, st, zero_lr=False):
+        """A frame's work on the buffers st, as `plan` has it (every host value of the loop comes from the plan):
+        the pose guess, its 7-vector, a fresh Adam, the camera loop, the result pose.  zero_lr: the capture's
+        warm-up, one iteration with every rate zero."""
+        cam, opt, best, best_loss = st["cam"], st["opt"], st["best"], st["best_loss"]
+        pre = st["pre"]
+        est = constant_speed_guess(pre, st["prev2"]) if plan.speed else pre
+        # the guess's 7-vector into the camera and the best pose in one launch (ABI v22)
+        ops.cam_vector_batch(est[None], cam.detach().view(1, 7), best.view(1, 7))
+        best_loss.fill_(float("inf"))
+        opt.reset_state()
+        opt.param_groups[0]["lr"] = 0.0 if zero_lr else plan.cam_lr
+        for _ in range(1 if zero_lr else plan.iters):
+            # (the iteration's loss launch also keeps the best pose, Tracker.py:245-247)
+            eng.iteration(cam, st["depth"], st["color"], None, opt, n=plan.n, seed=plan.seed,
+                          best=(best_loss, best), **Tracker._lr2(plan, zero=zero_lr))
+        ops.cam_pose(best, st["out"][:3])  # get_camera_from_tensor(best), one launch
 
     def _track_graph(self, gt_color, gt_depth, pre_c2w, prev2_c2w):
         """track_frame's whole per-frame work as ONE captured hipGraph, replayed for every frame: the pose
         guess (constant speed, Tracker.py:191-198), its camera 7-vector, a fresh Adam, the camera loop with
         device pixel draws and the device-side best-pose selection (Tracker.py:225-250), and the result pose.
-        Per frame the host copies the frame and the previous poses into persistent buffers and replays."""
+        Per frame the host copies the frame and the previous poses into persistent buffers and replays the
+        graph of the frame's FramePlan (ops.GraphCache: the capture sequence and what a key must hold)."""
         eng = self.engine()
-        dev = self.device
-        st = self._fstate
-        if st is None:
-            cam = torch.zeros(7, dtype=torch.float32, device=dev).requires_grad_(True)
-            out = torch.eye(4, dtype=torch.float32, device=dev)
-            st = self._fstate = {
-                "depth": torch.zeros(self.H, self.W, dtype=torch.float32, device=dev),
-                "color": torch.zeros(self.H, self.W, 3, dtype=torch.float32, device=dev),
-                "pre": torch.eye(4, dtype=torch.float32, device=dev), "prev2": torch.eye(4, dtype=torch.float32, device=dev),
-                "cam": cam, "opt": ops.FusedAdam([{"params": [cam], "lr": self.cam_lr}]),
-                "best": torch.zeros(7, dtype=torch.float32, device=dev),
-                "best_loss": torch.zeros((), dtype=torch.float64, device=dev), "out": out}
-            st["opt"].init_state()
-        cam, opt, best, best_loss = st["cam"], st["opt"], st["best"], st["best_loss"]
+        st = self._frame_state()
         st["depth"].copy_(gt_depth)
         st["color"].copy_(gt_color)
         st["pre"][:3].copy_(pre_c2w[:3])  # (the bottom row stays [0, 0, 0, 1])
-        speed = prev2_c2w is not None
-        if speed:
+        if prev2_c2w is not None:
             st["prev2"][:3].copy_(prev2_c2w[:3])
-        n, iters = self.tracking_pixels, self.num_cam_iters
-        lr2 = self._lr2()
+        plan = self._frame_plan(speed=prev2_c2w is not None)
+        draws = eng.eng.draws(plan.seed)
 
-        def frame(zero_lr=False):
-            pre = st["pre"]
-            est = constant_speed_guess(pre, st["prev2"]) if speed else pre
-            # the guess's 7-vector into the camera and the best pose in one launch (ABI v22)
-            ops.cam_vector_batch(est[None], cam.detach().view(1, 7), best.view(1, 7))
-            best_loss.fill_(float("inf"))
-            opt.reset_state()
-            for _ in range(1 if zero_lr else iters):
-                # (the iteration's loss launch also keeps the best pose, Tracker.py:245-247)
-                eng.iteration(cam, st["depth"], st["color"], None, opt, n=n, seed=self._draw_seed,
-                              best=(best_loss, best), **(dict(lr2, lr_quat=0.0) if zero_lr and lr2 else lr2))
-            ops.cam_pose(best, st["out"][:3])  # get_camera_from_tensor(best), one launch
+        def body():
+            self._frame(plan, eng, st)
+            return draws  # (kept with the graph that advances it: ops.GraphCache)
 
-        key = (iters, n, speed, self.seperate_LR)
-        if key not in self._graphs:
-            # one zero-lr eager iteration (both rates zero with seperate_LR; camera grad, Adam ticket, draw
-            # counter, caches made before capture);
-            # the draw stream is rewound, so the frame draws as it would have eagerly
-            ctr = eng.eng.draws(self._draw_seed).counter
-            ctr0 = ctr.clone()
-            opt.param_groups[0]["lr"] = 0.0
-            frame(zero_lr=True)
-            opt.param_groups[0]["lr"] = self.cam_lr
-            g = torch.cuda.CUDAGraph()
-            with ops.capture(g):
-                frame()
-            self._graphs[key] = g
-            ctr.copy_(ctr0)
-        self._graphs[key].replay()
+        g, _, _ = self._graphs.graph(plan, body, warm=lambda: self._frame(plan, eng, st, zero_lr=True),
+                                     rewind=[draws.counter])
+        g.replay()
         return st["out"].clone()

@@ -24,7 +24,8 @@ pytestmark = pytest.mark.gpu
 P = importlib.import_module("nice-slam_amd")
 
 
-def _run_two_calls(tiny, monkeypatch, graphs, ba=True):
+def _run_two_calls(tiny, monkeypatch, graphs, ba=True, between=None):
+    """between(mp): applied to the live Mapper after the first call (settings changed between calls)."""
     sc = Scene(tiny)
     cfg = base_cfg()
     cfg["mapping"].update(frustum_feature_selection=True, pixels=600)
@@ -38,27 +39,24 @@ def _run_two_calls(tiny, monkeypatch, graphs, ba=True):
     est = [sc.c2w.clone(), _nudged(sc.c2w, 0.01, (0.01, -0.005, 0.0))]
     kf = [{"gt_c2w": sc.c2w, "idx": i, "color": sc.color, "depth": sc.depth, "est_c2w": est[i].clone()}
           for i in range(2)]
-    outs, ngraphs = [], []
+    outs, ngraphs, keys = [], [], []
     for call, (ang, t) in enumerate(((-0.008, (0.0, 0.006, 0.004)), (0.012, (0.004, -0.002, 0.003)))):
+        if call == 1 and between is not None:
+            between(mp)
         cur = _nudged(sc.c2w, ang, t)
         out = mp.optimize_map(6, 1.0, 2 + call, sc.color, sc.depth, sc.c2w, kf, [0, 1], cur.clone())
         outs.append(out.detach().cpu() if out is not None else torch.zeros(4, 4))
-        ngraphs.append(sum(1 for k in mp._graphs if k[0] == "stage"))
+        ngraphs.append(sum(1 for k in mp._graphs if k.kind == "stage"))
+        keys.append(set(mp._graphs))
     torch.cuda.synchronize()
     grids = {k: v.detach().cpu().clone() for k, v in slam.shared_c.items()}
     dec = torch.cat([p.detach().reshape(-1).cpu() for p in mp.decoders.color_decoder.parameters()])
-    return {"losses": [float(x) for x in mp.loss_history], "grids": grids, "dec": dec, "outs": outs,
+    return {"losses": [float(x) for x in mp.loss_history], "grids": grids, "dec": dec, "outs": outs, "keys": keys,
             "kf1": kf[1]["est_c2w"].detach().cpu(), "ngraphs": ngraphs, "g0": {k: v.cpu() for k, v in sc.grids.items()}}
 
 
-@pytest.mark.parametrize("ba", [True, False])
-def test_optimize_map_graphs_match_eager(tiny, monkeypatch, ba):
-    """(ba=False: the captured runs also hold the ray prefetch chain of each stage run.)"""
-    eager = _run_two_calls(tiny, monkeypatch, graphs=False, ba=ba)
-    graph = _run_two_calls(tiny, monkeypatch, graphs=True, ba=ba)
-    assert eager["ngraphs"] == [0, 0]
-    # the first call captured one graph per stage run (middle, fine, colour); the second replayed them
-    assert graph["ngraphs"][0] == 3 and graph["ngraphs"][1] == 3
+def _assert_graphs_match_eager(graph, eager):
+    """The file's tolerances: losses rtol 1e-4, updates rel-L2 1e-3."""
     assert len(graph["losses"]) == len(eager["losses"]) == 12
     np.testing.assert_allclose(graph["losses"], eager["losses"], rtol=1e-4)
     report = {}
@@ -70,6 +68,60 @@ def test_optimize_map_graphs_match_eager(tiny, monkeypatch, ba):
     report["kf1"] = rel_l2(graph["kf1"], eager["kf1"])
     print(report)
     assert all(v < 1e-3 for v in report.values()), report
+
+
+@pytest.mark.parametrize("ba", [True, False])
+def test_optimize_map_graphs_match_eager(tiny, monkeypatch, ba):
+    """(ba=False: the captured runs also hold the ray prefetch chain of each stage run.)"""
+    eager = _run_two_calls(tiny, monkeypatch, graphs=False, ba=ba)
+    graph = _run_two_calls(tiny, monkeypatch, graphs=True, ba=ba)
+    assert eager["ngraphs"] == [0, 0]
+    # the first call captured one graph per stage run (middle, fine, colour); the second replayed them
+    assert graph["ngraphs"][0] == 3 and graph["ngraphs"][1] == 3
+    _assert_graphs_match_eager(graph, eager)
+
+
+def _halve_colour_rates(mp):
+    mp.cfg["mapping"]["stage"]["color"]["color_lr"] *= 0.5
+    mp.BA_cam_lr *= 0.5
+
+
+def test_graphs_follow_changed_rates(tiny, monkeypatch):
+    """The colour stage's colour-grid rate and the BA camera rate halved between two calls: both are baked into
+    the colour graph's Adam launches and are part of its StagePlan, so the second call captures a new colour
+    graph (the middle and fine graphs are reused) and matches an eager Mapper given the same two calls."""
+    eager = _run_two_calls(tiny, monkeypatch, graphs=False, between=_halve_colour_rates)
+    graph = _run_two_calls(tiny, monkeypatch, graphs=True, between=_halve_colour_rates)
+    first, second = ({k for k in ks if k.kind == "stage"} for ks in graph["keys"])
+    assert graph["ngraphs"] == [3, 4] and first < second
+    (new,) = second - first
+    (old,) = (k for k in first if k.stage == "color")
+    assert new.stage == "color" and new.lrs[4] == old.lrs[4] * 0.5 and new.cam_lr == old.cam_lr * 0.5
+    assert new.lrs[:4] == old.lrs[:4]
+    _assert_graphs_match_eager(graph, eager)
+    # (the change is visible at these tolerances: the unchanged rates give another second call)
+    stale = _run_two_calls(tiny, monkeypatch, graphs=False)
+    assert rel_l2(eager["grids"]["grid_color"] - eager["g0"]["grid_color"],
+                  stale["grids"]["grid_color"] - stale["g0"]["grid_color"]) > 1e-2
+
+
+def _colour_refinement_flags(mp):
+    mp.fix_color = True
+    mp.frustum_feature_selection = False
+
+
+def test_graphs_follow_the_colour_refinement_flags(tiny, monkeypatch):
+    """fix_color and frustum_feature_selection switched as map_frame's colour-refinement pass does, with no
+    manual clear: the second call gets an optimiser without the colour decoder, a setup without the frustum
+    kernel and stage graphs of its own, and matches an eager Mapper given the same two calls."""
+    eager = _run_two_calls(tiny, monkeypatch, graphs=False, between=_colour_refinement_flags)
+    graph = _run_two_calls(tiny, monkeypatch, graphs=True, between=_colour_refinement_flags)
+    assert graph["ngraphs"] == [3, 6]
+    setups = [{k for k in ks if k.kind == "setup"} for ks in graph["keys"]]
+    assert len(setups[0]) == 1 and len(setups[1]) == 2
+    (new,) = setups[1] - setups[0]
+    assert new.frustum is False and new.trainable == ()
+    _assert_graphs_match_eager(graph, eager)
 
 
 def test_coarse_mapper_fused_matches_autograd(tiny, monkeypatch):
@@ -113,11 +165,7 @@ def test_coarse_mapper_fused_matches_autograd(tiny, monkeypatch):
     assert max(other_f.values()) == 0.0 and max(other_a.values()) == 0.0
 
 
-def test_tracker_graph_matches_eager_device_draws(tiny):
-    """Tracker.track_frame's captured camera loop (one hipGraph per frame, device draws) == the same loop
-    run eagerly on the tracking engine with the same draw stream — bit for bit (the camera chain is
-    deterministic: no float atomics), on the frame that captures the graph and on one that replays it."""
-    cfg = base_cfg()
+def _tracker_frames(tiny):
     sc = Scene(tiny)
     c2w = torch.cat([sc.c2w[:3], torch.tensor([[0, 0, 0, 1.0]])], 0).cuda()
     pres = []
@@ -125,20 +173,21 @@ def test_tracker_graph_matches_eager_device_draws(tiny):
         pre = c2w.clone()
         pre[:3, 3] += d
         pres.append(pre)
-    tr = P.Tracker(cfg, None, sc.slam(cfg))
-    tr._draw_seed = 77
-    got = [tr.track_frame(k + 1, sc.color.cuda(), sc.depth.cuda(), c2w, pre_c2w=pre) for k, pre in enumerate(pres)]
-    assert len(tr._graphs) == 1
-    # eager replica: the same engine calls, draws from the same stream (counter 0, advancing per iteration)
+    return sc, c2w, pres
+
+
+def _eager_tracker_loop(cfg, sc, pres, lrs):
+    """The eager replica of the captured frame: the same engine calls, draws from the same stream (counter 0,
+    advancing per iteration), frame k with the camera rate lrs[k]."""
     tr2 = P.Tracker(cfg, None, sc.slam(cfg))
     tr2.update_para_from_mapping()
     eng = tr2.engine()
     ref = []
-    for pre in pres:
+    for pre, lr in zip(pres, lrs):
         # (the graph forms the guess's 7-vector and the result pose with nslam_cam_vector_batch / nslam_cam_pose)
         cam = P.ops.cam_vector_batch(pre[None].contiguous(), torch.empty(1, 7, device="cuda"))[0]
         cam = cam.clone().requires_grad_(True)
-        opt = P.ops.FusedAdam([{"params": [cam], "lr": cfg["tracking"]["lr"]}])
+        opt = P.ops.FusedAdam([{"params": [cam], "lr": lr}])
         best, best_loss = cam.detach().clone(), torch.full((), float("inf"), dtype=torch.float64, device="cuda")
         for _ in range(cfg["tracking"]["iters"]):
             loss = eng.iteration(cam, sc.depth.cuda(), sc.color.cuda(), None, opt, n=cfg["tracking"]["pixels"], seed=77)
@@ -148,6 +197,41 @@ def test_tracker_graph_matches_eager_device_draws(tiny):
         pose = torch.eye(4, device="cuda")
         P.ops.cam_pose(best.contiguous(), pose[:3])
         ref.append(pose)
+    return ref
+
+
+def test_tracker_graph_matches_eager_device_draws(tiny):
+    """Tracker.track_frame's captured camera loop (one hipGraph per frame, device draws) == the same loop
+    run eagerly on the tracking engine with the same draw stream — bit for bit (the camera chain is
+    deterministic: no float atomics), on the frame that captures the graph and on one that replays it."""
+    cfg = base_cfg()
+    sc, c2w, pres = _tracker_frames(tiny)
+    tr = P.Tracker(cfg, None, sc.slam(cfg))
+    tr._draw_seed = 77
+    got = [tr.track_frame(k + 1, sc.color.cuda(), sc.depth.cuda(), c2w, pre_c2w=pre) for k, pre in enumerate(pres)]
+    assert len(tr._graphs) == 1
+    ref = _eager_tracker_loop(cfg, sc, pres, [cfg["tracking"]["lr"]] * 2)
     for a, b in zip(got, ref):
         assert torch.equal(a, b), (a - b).abs().max()
     assert not torch.equal(got[0], pres[0])  # the loop moved the pose
+
+
+def test_tracker_graph_follows_a_changed_rate(tiny):
+    """cam_lr halved after the first frame: the second frame gets a graph of its own (the rate is baked into
+    the camera tail's arguments and is part of the FramePlan) and equals the eager loop at the new rate bit
+    for bit."""
+    cfg = base_cfg()
+    sc, c2w, pres = _tracker_frames(tiny)
+    tr = P.Tracker(cfg, None, sc.slam(cfg))
+    tr._draw_seed = 77
+    lr = cfg["tracking"]["lr"]
+    got = [tr.track_frame(1, sc.color.cuda(), sc.depth.cuda(), c2w, pre_c2w=pres[0])]
+    tr.cam_lr = lr * 0.5
+    got.append(tr.track_frame(2, sc.color.cuda(), sc.depth.cuda(), c2w, pre_c2w=pres[1]))
+    assert len(tr._graphs) == 2
+    assert sorted(k.cam_lr for k in tr._graphs) == [lr * 0.5, lr]
+    ref = _eager_tracker_loop(cfg, sc, pres, [lr, lr * 0.5])
+    for a, b in zip(got, ref):
+        assert torch.equal(a, b), (a - b).abs().max()
+    stale = _eager_tracker_loop(cfg, sc, pres, [lr, lr])  # (what replaying the first frame's graph would give)
+    assert not torch.equal(got[1], stale[1])

@@ -271,12 +271,12 @@ def test_run_replays_graphs_off_the_vis_frames(tmp_path, monkeypatch, tiny):
     # tracking: frames 2 and 4 visualise (eager), 1 and 3 replay the frame graph
     assert calls.replays["track"] == {1: 1, 2: 0, 3: 1, 4: 0}
     # (two graphs: frame 1 has no second-last pose for the constant-speed guess, frame 3 has)
-    assert sorted(k[2] for k in slam.tracker._graphs) == [False, True]
+    assert sorted(k.speed for k in slam.tracker._graphs) == [False, True]
     # mapping: the first frame's one-off schedule and frame 3 (it visualises) run eagerly; the others replay
     # the setup graph and one graph per stage
     assert calls.replays["map"][0] == 0 and calls.replays["map"][3] == 0
     assert all(calls.replays["map"][i] >= 3 for i in (1, 2, 4)), calls.replays["map"]
-    assert any(k[0] == "stage" for k in slam.mapper._graphs)
+    assert any(k.kind == "stage" for k in slam.mapper._graphs)
     est = slam.estimate_c2w_list
     assert torch.equal(est[0], poses[0])
     for i in range(1, 5):

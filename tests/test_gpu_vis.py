@@ -95,9 +95,10 @@ def test_vis_writes_the_twins_jpeg_and_touches_nothing(scene, tmp_path):
     bottom = torch.tensor([[0, 0, 0, 1.0]], device=DEV)
     c2w44 = torch.cat([P.common.get_camera_from_tensor(cam), bottom], 0)  # the same pose in both forms
     eng = mp.engine()
-    state = _tensors(mp._fopt.state, []) + [eng.draws(mp._draw_seed).counter]
+    (fopt,) = mp._fopt.values()  # (the one optimiser the call made)
+    state = _tensors(fopt.state, []) + [eng.draws(mp._draw_seed).counter]
     state += list(slam.shared_c.values()) + [p.data for p in slam.shared_decoders.parameters()]
-    assert len(_tensors(mp._fopt.state, [])) > 0
+    assert len(_tensors(fopt.state, [])) > 0
     before = [t.clone() for t in state]
     # off its (idx, iter) condition: a no-op
     v.vis(5, 1, depth, color, cam, slam.shared_c, slam.shared_decoders)
